@@ -5,13 +5,16 @@ N GPUs).  A step = forward + PoseLoss(1, 10, geodesic) + backward +
 clip_grad_norm_(1.0) + AdamW, the body of train_rgbd_geometric.py:97-115, on
 synthetic device-resident inputs of the reference's shapes, bf16 trunk.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N)
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
-"roofline" for the dominant kernel (HIP events, grouped by kernel symbol) and
-"cpu_baseline" (the oracle's torch-CPU fp32 restatement of the same step,
-rank 0 only, bounded sample).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps,
+writes the last step's outputs if --dump-outputs is given, and prints the headline
+line (metric / value / unit / ms_per_step ...).  --full adds every other measurement
+to that line: "roofline" for the dominant kernel (HIP events, grouped by kernel
+symbol), the fp32 training line, the side configurations and "cpu_baseline" (the
+oracle's torch-CPU fp32 restatement of the same step, rank 0 only, bounded sample);
+the --no-* options drop single parts of a --full run.
 """
 import argparse
 import json
@@ -175,12 +178,37 @@ def cpu_baseline_add(pts, diam, args, n=32):
                      round(n / dt, 2), "samples/s")
 
 
-def main():
+DUMP_SAMPLE = 4 * 1024 * 1024   # elements kept of each of the parameter / gradient arenas (16 MB as float32)
+
+
+def dump_outputs(tr, out_dir):
+    """What the last step of `tr` handed its caller, as float32 <name>.npy files in
+    `out_dir` (about 33 MB): the loss, the predicted rotations / translations, the
+    gradient norm the clip saw, the BatchNorm running statistics, and a fixed seeded
+    sample (DUMP_SAMPLE elements, the same indices in every run) of the updated
+    parameters and of the gradients in the trainer's flat arena."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator().manual_seed(20240229)
+    idx = torch.randint(0, tr.arena.numel, (min(DUMP_SAMPLE, tr.arena.numel),), generator=g).sort().values.to(tr.dev)
+    bn = [b.detach().reshape(-1).float() for n, b in tr.model.named_buffers() if "running" in n]
+    arrays = {"loss": tr.loss.reshape(1), "rot": tr.rot, "trans": tr.trans, "grad_norm": tr.norm.reshape(1),
+              "bn_running_stats": torch.cat(bn), "params_sample": tr.arena.flat[idx], "grads_sample": tr.arena.grad[idx]}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the in-step roofline, the fp32 training line, the side configurations and the CPU "
+                         "baselines (each can be dropped again with its --no-* option)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-profile", action="store_true")
     ap.add_argument("--eager", action="store_true", help="no hipGraph capture")
@@ -188,7 +216,14 @@ def main():
     ap.add_argument("--no-fp32", action="store_true", help="skip the fp32 (reference precision) training line")
     ap.add_argument("--pmc-bf16", default=None, help="PMC summary json for the bf16 roofline traffic")
     ap.add_argument("--pmc-f32", default=None, help="PMC summary json for the fp32 roofline traffic")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if not args.full:   # a plain run measures the headline figure only
+        args.no_cpu_baseline = args.no_kernel_profile = args.no_side = args.no_fp32 = True
+    return args
+
+
+def main():
+    args = parse_args()
     if args.pmc_bf16:
         PMC_SUMMARY["bf16"] = args.pmc_bf16
     if args.pmc_f32:
@@ -239,6 +274,8 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         el = t.item()
     loss = tr.loss.item()
+    if args.dump_outputs and rank == 0:   # before anything below runs the trainer again
+        dump_outputs(tr, args.dump_outputs)
     ms = el / args.steps * 1e3
     value = world * B * args.steps / el
 
@@ -260,7 +297,7 @@ def main():
     # under a live RCCL group (whose watchdog thread polls collective events meanwhile;
     # tests/rccl_worker.py); the fp32 / side / CPU lines are one-GPU figures: N = 1 only
     solo = world == 1
-    if not solo:
+    if args.full and not solo:
         result["side_measurements"] = "N=1 only (fp32_train, side_configs, cpu_baseline); roofline on rank 0"
     if rank == 0 and not args.no_kernel_profile:
         try:

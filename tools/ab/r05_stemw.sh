@@ -12,5 +12,5 @@ timeout -k 10 300 python -u tools/conv_bench.py --graph --only 0 --passes wgrad,
 grep -v amdgpu.ids $OUT/stem_wgrad.txt
 bash tools/step_trace.sh $TAG || exit 1
 head -3 gpurun_out/trace_$TAG/window.txt; grep -E "wgrad_lds_kernel|conv_wgrad_kernel|ILi6E|Li6ELi2" gpurun_out/trace_$TAG/window.txt | head
-timeout -k 10 300 python -u bench.py --steps 20 > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --steps 20 > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
 python -c "import json;d=json.load(open('$OUT/bench.json'));print(d['value'],d['ms_per_step'],d['fp32_train']['ms_per_step'],d['forward_roofline_eval']['fwd_ms'])"

@@ -4,8 +4,8 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out/${1:-r06i}; VAR=$2
 mkdir -p $OUT
-timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-side --no-fp32 --no-cpu-baseline > $OUT/base.json 2> $OUT/base.err || { tail $OUT/base.err; exit 1; }
-POSE6D_LIB=$VAR timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-side --no-fp32 --no-cpu-baseline > $OUT/var.json 2> $OUT/var.err || { tail $OUT/var.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-side --no-fp32 --no-cpu-baseline > $OUT/base.json 2> $OUT/base.err || { tail $OUT/base.err; exit 1; }
+POSE6D_LIB=$VAR timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-side --no-fp32 --no-cpu-baseline > $OUT/var.json 2> $OUT/var.err || { tail $OUT/var.err; exit 1; }
 python - $OUT <<'PY'
 import json, sys
 d = sys.argv[1]

@@ -12,7 +12,7 @@ timeout -k 10 300 python -u tools/ab_attr.py pose6d.trunk.TrunkEngine.bn_fused_f
 cat $OUT/ab_bf16.txt
 timeout -k 10 300 python -u tools/ab_attr.py pose6d.trunk.TrunkEngine.bn_fused_finalize_act --rounds 3 --dtype f32 > $OUT/ab_f32.txt 2>&1 || { tail $OUT/ab_f32.txt; exit 1; }
 cat $OUT/ab_f32.txt
-timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-side --no-fp32 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-side --no-fp32 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
 python - $OUT <<'PY'
 import json, sys
 r = json.loads(open(f"{sys.argv[1]}/bench.json").read().strip().splitlines()[-1])
