@@ -25,14 +25,8 @@ __global__ void rownorm_fwd_kernel(const float* __restrict__ x, float* __restric
   for (int i = 0; i < D; ++i) y[b * D + i] = xr[i] / d;
 }
 
-// mode 0: y = x / max(n, eps);   mode 1: y = x / (n + eps)
-__global__ void rownorm_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dx,
-                                   int64_t B, int D, int mode) {
-  const int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  const float* xr = x + b * D;
-  const float* g = dy + b * D;
-  const float n = l2(xr, D);
+// back through one row of y = x / max(n, eps) (mode 0) or y = x / (n + eps) (mode 1), n = ||x||
+__device__ __forceinline__ void rownorm_bwd_row(const float* xr, const float* g, float n, int D, int mode, float* dx) {
   float xg = 0.f;
   for (int i = 0; i < D; ++i) xg = fmaf(xr[i], g[i], xg);
   if (mode == 0) {
@@ -40,15 +34,23 @@ __global__ void rownorm_bwd_kernel(const float* __restrict__ x, const float* __r
       // dx = dy / n - x (x.dy) / n^3
       const float inv = 1.0f / n;
       const float c = xg * inv * inv * inv;
-      for (int i = 0; i < D; ++i) dx[b * D + i] = g[i] * inv - xr[i] * c;
+      for (int i = 0; i < D; ++i) dx[i] = g[i] * inv - xr[i] * c;
     } else {
-      for (int i = 0; i < D; ++i) dx[b * D + i] = g[i] / kNormEps;   // clamp_min: no grad to n
+      for (int i = 0; i < D; ++i) dx[i] = g[i] / kNormEps;   // clamp_min: no grad to n
     }
   } else {
     const float d = n + kGeoEps;
     const float c = n > 0.f ? xg / (d * d * n) : 0.f;                 // norm grad is 0 at 0
-    for (int i = 0; i < D; ++i) dx[b * D + i] = g[i] / d - xr[i] * c;
+    for (int i = 0; i < D; ++i) dx[i] = g[i] / d - xr[i] * c;
   }
+}
+
+__global__ void rownorm_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dx,
+                                   int64_t B, int D, int mode) {
+  const int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const float* xr = x + b * D;
+  rownorm_bwd_row(xr, dy + b * D, l2(xr, D), D, mode, dx + b * D);
 }
 
 __device__ __forceinline__ void load_K(const float* K, int batched, int64_t b, float& fx, float& fy, float& cx,
@@ -157,16 +159,10 @@ __device__ float rot_term(const float* pr, const float* gr, int mode, float* dpr
   return val;
 }
 
-__global__ __launch_bounds__(kThreads) void pose_loss_fwd_kernel(const float* __restrict__ pr, const float* __restrict__ pt,
-                                                                 const float* __restrict__ gr, const float* __restrict__ gt,
-                                                                 int64_t B, float wr, float wt, int mode,
-                                                                 float* __restrict__ loss) {
+// the one-block loss reduction: each thread's rotation / translation sums -> wave_sum,
+// then the per-wave partials summed by thread 0 (fixed order: deterministic)
+__device__ __forceinline__ void block_loss(float sr, float st, int64_t B, float wr, float wt, float* loss) {
   __shared__ float red[2][kThreads / 64];
-  float sr = 0.f, st = 0.f;
-  for (int64_t b = threadIdx.x; b < B; b += kThreads) {
-    sr += rot_term(pr + 4 * b, gr + 4 * b, mode, nullptr, 0.f);
-    for (int i = 0; i < 3; ++i) st += fabsf(pt[3 * b + i] - gt[3 * b + i]);
-  }
   sr = p6::wave_sum(sr);
   st = p6::wave_sum(st);
   if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sr; red[1][threadIdx.x >> 6] = st; }
@@ -176,6 +172,18 @@ __global__ __launch_bounds__(kThreads) void pose_loss_fwd_kernel(const float* __
     for (int i = 0; i < kThreads / 64; ++i) { a += red[0][i]; c += red[1][i]; }
     loss[0] = wr * (a / (float)B) + wt * (c / (float)(3 * B));
   }
+}
+
+__global__ __launch_bounds__(kThreads) void pose_loss_fwd_kernel(const float* __restrict__ pr, const float* __restrict__ pt,
+                                                                 const float* __restrict__ gr, const float* __restrict__ gt,
+                                                                 int64_t B, float wr, float wt, int mode,
+                                                                 float* __restrict__ loss) {
+  float sr = 0.f, st = 0.f;
+  for (int64_t b = threadIdx.x; b < B; b += kThreads) {
+    sr += rot_term(pr + 4 * b, gr + 4 * b, mode, nullptr, 0.f);
+    for (int i = 0; i < 3; ++i) st += fabsf(pt[3 * b + i] - gt[3 * b + i]);
+  }
+  block_loss(sr, st, B, wr, wt, loss);
 }
 
 __global__ void pose_loss_bwd_kernel(const float* __restrict__ pr, const float* __restrict__ pt,
@@ -204,7 +212,6 @@ __global__ __launch_bounds__(kThreads) void geo_head_loss_kernel(
     const float* __restrict__ K, int Kb, const float* __restrict__ gr, const float* __restrict__ gt, int64_t B,
     float wr, float wt, int mode, float* __restrict__ rot, float* __restrict__ trans, float* __restrict__ loss,
     float* __restrict__ draw, float* __restrict__ dtrans) {
-  __shared__ float red[2][kThreads / 64];
   float sr = 0.f, st = 0.f;
   const float grot_scale = wr / (float)B, c = wt / (float)(3 * B);
   for (int64_t b = threadIdx.x; b < B; b += kThreads) {
@@ -235,24 +242,38 @@ __global__ __launch_bounds__(kThreads) void geo_head_loss_kernel(
       dtrans[3 * b + i] = e > 0.f ? c : (e < 0.f ? -c : 0.f);
     }
     // back through F.normalize (rownorm_bwd mode 0)
-    if (n > kNormEps) {
-      float xg = 0.f;
-      for (int i = 0; i < 4; ++i) xg = fmaf(xr[i], drot[i], xg);
-      const float inv = 1.0f / n, cc = xg * inv * inv * inv;
-      for (int i = 0; i < 4; ++i) draw[4 * b + i] = drot[i] * inv - xr[i] * cc;
-    } else {
-      for (int i = 0; i < 4; ++i) draw[4 * b + i] = drot[i] / kNormEps;
+    rownorm_bwd_row(xr, drot, n, 4, 0, draw + 4 * b);
+  }
+  block_loss(sr, st, B, wr, wt, loss);
+}
+
+// PoseNetRGB's head + loss: geo_head_loss_kernel's sibling without the pinhole -- the
+// translation head's output is an input.  Per sample rot = normalize(raw) (nmode as
+// rownorm_*), the PoseLoss terms, d loss / d rot for dloss = 1 taken back through the
+// normalise into draw, and dtrans = sign(trans - gt) * wt / (3 B); the loss reduced in
+// pose_loss_fwd's order (rot / loss / dtrans bit-identical to the separate calls).
+__global__ __launch_bounds__(kThreads) void quat_head_loss_kernel(
+    const float* __restrict__ raw, const float* __restrict__ trans, const float* __restrict__ gr,
+    const float* __restrict__ gt, int64_t B, float wr, float wt, int mode, int nmode, float* __restrict__ rot,
+    float* __restrict__ loss, float* __restrict__ draw, float* __restrict__ dtrans) {
+  float sr = 0.f, st = 0.f;
+  const float grot_scale = wr / (float)B, c = wt / (float)(3 * B);
+  for (int64_t b = threadIdx.x; b < B; b += kThreads) {
+    const float* xr = raw + 4 * b;
+    const float n = l2(xr, 4);
+    const float d = nmode == 0 ? fmaxf(n, kNormEps) : n + kGeoEps;
+    float q[4];
+    for (int i = 0; i < 4; ++i) { q[i] = xr[i] / d; rot[4 * b + i] = q[i]; }
+    float drot[4];
+    sr += rot_term(q, gr + 4 * b, mode, drot, grot_scale);
+    for (int i = 0; i < 3; ++i) {
+      const float e = trans[3 * b + i] - gt[3 * b + i];
+      st += fabsf(e);
+      dtrans[3 * b + i] = e > 0.f ? c : (e < 0.f ? -c : 0.f);
     }
+    rownorm_bwd_row(xr, drot, n, 4, nmode, draw + 4 * b);
   }
-  sr = p6::wave_sum(sr);
-  st = p6::wave_sum(st);
-  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sr; red[1][threadIdx.x >> 6] = st; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float a = 0.f, cc = 0.f;
-    for (int i = 0; i < kThreads / 64; ++i) { a += red[0][i]; cc += red[1][i]; }
-    loss[0] = wr * (a / (float)B) + wt * (cc / (float)(3 * B));
-  }
+  block_loss(sr, st, B, wr, wt, loss);
 }
 
 inline unsigned nblk(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
@@ -336,6 +357,20 @@ extern "C" int pose6d_geo_head_loss(const float* raw, const float* depth_raw, in
   geo_head_loss_kernel<<<1, kThreads, 0, p6::stream_of(stream)>>>(raw, depth_raw, H, W, bbox_center, K, K_batched,
                                                                   gt_rot, gt_trans, B, rot_weight, trans_weight,
                                                                   rot_mode, rot, trans, loss, grad_raw, grad_trans);
+  P6_LAUNCH_CHECK();
+  return POSE6D_OK;
+}
+
+extern "C" int pose6d_quat_head_loss(const float* raw, const float* trans, const float* gt_rot, const float* gt_trans,
+                                     int64_t B, float rot_weight, float trans_weight, int32_t rot_mode,
+                                     int32_t norm_mode, float* rot, float* loss, float* grad_raw, float* grad_trans,
+                                     void* stream) {
+  P6_CHECK_ARG(B > 0, "pose6d_quat_head_loss: empty batch (the reference's mean would be NaN)");
+  P6_CHECK_ARG(rot_mode == 0 || rot_mode == 1, "pose6d_quat_head_loss: bad rot_mode %d", rot_mode);
+  P6_CHECK_ARG(norm_mode == 0 || norm_mode == 1, "pose6d_quat_head_loss: bad norm_mode %d", norm_mode);
+  quat_head_loss_kernel<<<1, kThreads, 0, p6::stream_of(stream)>>>(raw, trans, gt_rot, gt_trans, B, rot_weight,
+                                                                   trans_weight, rot_mode, norm_mode, rot, loss,
+                                                                   grad_raw, grad_trans);
   P6_LAUNCH_CHECK();
   return POSE6D_OK;
 }

@@ -178,8 +178,14 @@ class HeadEngine:
         self._saved_gen = -1 if skip >= 0 else self.generation   # fused: no backward state
         return cur
 
-    def backward(self, dy, grad_of, accumulate=False, need_dx=True, wgrad_stream=None):
-        """wgrad_stream (a torch.cuda.Stream, optional): the Linear weight gradients,
+    def backward(self, dy, grad_of, accumulate=False, need_dx=True, wgrad_stream=None, dx_out=None,
+                 dx_accumulate=False):
+        """dx_out (a (B, in) fp32 device tensor, optional): the first stage's data-gradient
+        GEMM stores the head's input gradient there instead of the engine's own buffer, and
+        with dx_accumulate=True adds it to what dx_out holds (beta = 1: heads that read one
+        feature sum their input gradients with no extra launch); returned as the result.
+        The first stage must then be a Linear.
+        wgrad_stream (a torch.cuda.Stream, optional): the Linear weight gradients,
         which nothing downstream of the head's data gradient reads, run there -- each
         after the current stream's work up to its launch -- so they overlap the trunk
         backward; the caller joins it (current_stream().wait_stream) before anything
@@ -191,6 +197,17 @@ class HeadEngine:
         B = dy.shape[0]
         g = dy.detach().float().contiguous()
         acc = int(accumulate)
+        if dx_out is None:
+            if dx_accumulate:
+                raise Pose6dError("HeadEngine.backward: dx_accumulate needs dx_out")
+        else:
+            require_device(dx_out)
+            st0 = self.stages[0]
+            if st0.kind != "linear" or not need_dx:
+                raise Pose6dError("HeadEngine.backward: dx_out needs a Linear first stage and need_dx")
+            if (dx_out.dtype != torch.float32 or not dx_out.is_contiguous()
+                    or tuple(dx_out.shape) != (B, st0.mod.in_features)):
+                raise Pose6dError("HeadEngine.backward: dx_out must be a contiguous fp32 (B, in_features) tensor")
         for idx in range(len(self.stages) - 1, -1, -1):
             st = self.stages[idx]
             last = idx == 0
@@ -206,6 +223,10 @@ class HeadEngine:
                      grad_of(m.bias) if m.bias is not None else None, N, K, B, acc, ws_)
                 if last and not need_dx:
                     return None
+                if last and dx_out is not None:
+                    call("gemm_f32", g, N, 1, m.weight.detach(), K, 1, dx_out, K, None, B, K, N, 1.0,
+                         1.0 if dx_accumulate else 0.0, self.ws, self.ws.numel(), st_)
+                    return dx_out
                 call("gemm_f32", g, N, 1, m.weight.detach(), K, 1, st.dx, K, None, B, K, N, 1.0, 0.0, self.ws,
                      self.ws.numel(), st_)
             elif st.kind == "bn1d":

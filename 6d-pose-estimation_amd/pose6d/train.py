@@ -2,6 +2,8 @@
 (forward + PoseLoss(1, 10, geodesic) + backward + clip_grad_norm_(1.0) + AdamW),
 i.e. the per-batch body of the reference's train() loop
 (scripts/training/train_rgbd_geometric.py:97-115), without autograd or host syncs.
+RGBTrainer (at the end) is the same step for PoseNetRGB's two heads
+(scripts/training/train_rgb.py:95-141).
 
 MI355X design:
   * one flat fp32 arena for parameters / gradients / AdamW moments (the module's
@@ -85,6 +87,9 @@ class FlatArena:
 class RGBDGeometricTrainer:
     """Fused, graph-captured training step for PoseNetRGBDGeometric."""
 
+    # POSE6D_HEAD_WGRAD_SIDE applies (RGBTrainer's step is one chain whatever it says)
+    _head_wgrad_side = True
+
     def __init__(self, model, batch, dtype=torch.bfloat16, lr=1e-4, weight_decay=1e-4, max_norm=1.0,
                  betas=(0.9, 0.999), eps=1e-8, rot_weight=1.0, trans_weight=10.0, process_group=None,
                  bucket_mb=25.0, tail_mb=2.0, force_buckets=False, pack_in_adamw=True):
@@ -96,8 +101,7 @@ class RGBDGeometricTrainer:
         self.trunk = TrunkEngine(model.backbone, 3)
         self.trunk.set_dtype(dtype)
         self.trunk.prepare(batch, 224, 224, dtype, dev)
-        self.head = HeadEngine(model.rot_head)
-        order = self.head.params_in_grad_order() + self.trunk.params_in_grad_order()
+        order = self._build_heads(model) + self.trunk.params_in_grad_order()
         assert len(order) == len(list(model.parameters())) and {id(p) for p in order} == \
             {id(p) for p in model.parameters()}
         self.arena = FlatArena(order, dev)
@@ -141,6 +145,12 @@ class RGBDGeometricTrainer:
         self.pg = process_group
         self.graphs = None
         self._buckets(bucket_mb, tail_mb)
+
+    def _build_heads(self, model):
+        """The head engines; returns their parameters in gradient-completion order (the
+        arena's prefix, ahead of the trunk's)."""
+        self.head = HeadEngine(model.rot_head)
+        return self.head.params_in_grad_order()
 
     # ------------------------------------------------------------- packed weights
     def _build_jobs(self):
@@ -203,8 +213,8 @@ class RGBDGeometricTrainer:
              self.draw, self.dtrans, st)
         return raw
 
-    def _head_backward(self):
-        return self.head.backward(self.draw, self.arena.grad_of)
+    def _head_backward(self, wgrad_stream=None):
+        return self.head.backward(self.draw, self.arena.grad_of, wgrad_stream=wgrad_stream)
 
     def _optimizer(self):
         st = stream()
@@ -248,8 +258,8 @@ class RGBDGeometricTrainer:
         nodes into a chain)."""
         self._pack()
         self._forward_loss(*data)
-        side = self._side_stream() if branch and POSE6D_HEAD_WGRAD_SIDE else None
-        dfeat = self.head.backward(self.draw, self.arena.grad_of, wgrad_stream=side)
+        side = self._side_stream() if branch and POSE6D_HEAD_WGRAD_SIDE and self._head_wgrad_side else None
+        dfeat = self._head_backward(wgrad_stream=side)
         self.trunk.backward(dfeat, self.arena.grad_of)
         if side is not None:
             torch.cuda.current_stream().wait_stream(side)
@@ -442,3 +452,42 @@ class RGBDGeometricTrainer:
         if "optimizer_state_dict" in ckpt:
             self.load_optimizer_state_dict(ckpt["optimizer_state_dict"])
         return ckpt.get("epoch", -1) + 1
+
+
+class RGBTrainer(RGBDGeometricTrainer):
+    """Fused, graph-captured training step for PoseNetRGB: the per-batch body of the
+    reference's scripts/training/train_rgb.py:95-141 (forward + PoseLoss(1, 10, geodesic)
+    + backward + clip_grad_norm_(1.0) + AdamW) on RGBDGeometricTrainer's machinery -- one
+    ResNet50 trunk, one arena, the same optimizer launches, buckets, graphs and
+    checkpoints.  data = (rgb, gt_rot, gt_trans).
+
+    Two BN-MLP heads read the trunk's [B, 2048] feature (dropout salts 1 and 2, as
+    models/pose_net_rgb.py).  Arena order = gradient-completion order: rot_head, then
+    trans_head, then the trunk.  The translation head's input gradient is added to the
+    rotation head's by its own data-gradient GEMM (beta = 1), so the trunk's dfeat costs
+    no extra launch.  The captured step is one chain: no side stream, whatever
+    POSE6D_HEAD_WGRAD_SIDE says."""
+
+    _head_wgrad_side = False
+
+    def _build_heads(self, model):
+        self.head = HeadEngine(model.rot_head)
+        self.trans_head = HeadEngine(model.trans_head)
+        return self.head.params_in_grad_order() + self.trans_head.params_in_grad_order()
+
+    def _forward_loss(self, rgb, gt_rot, gt_trans):
+        st = stream()
+        feat = self.trunk.forward(rgb, True, pack=False)
+        raw = self.head.forward(feat, True, seed_dev=self.seed, salt=1)
+        trans = self.trans_head.forward(feat, True, seed_dev=self.seed, salt=2)
+        # F.normalize + PoseLoss fwd/bwd + normalize bwd: one launch (the arithmetic of the
+        # rownorm_* / pose_loss_* entry points); self.trans keeps the step's translation
+        call("quat_head_loss", raw, trans, gt_rot, gt_trans, self.B, self.wr, self.wt, 0, 0, self.rot, self.loss,
+             self.draw, self.dtrans, st)
+        self.trans = trans
+        return raw
+
+    def _head_backward(self, wgrad_stream=None):
+        dfeat = self.head.backward(self.draw, self.arena.grad_of)
+        # fan-in: both heads read the same feature -> dfeat = sum of their input gradients
+        return self.trans_head.backward(self.dtrans, self.arena.grad_of, dx_out=dfeat, dx_accumulate=True)

@@ -139,6 +139,16 @@ int pose6d_geo_head_loss(const float *raw, const float *depth_raw, int32_t H, in
                          float rot_weight, float trans_weight, int32_t rot_mode, float *rot, float *trans,
                          float *loss, float *grad_raw, float *grad_trans, void *stream);
 
+/* PoseNetRGB's training-step head + loss in one launch (pose6d_geo_head_loss without the
+ * pinhole): rot = normalize(raw) with norm_mode as pose6d_rownorm_* (0: F.normalize,
+ * pose_net_rgb.py:61; 1: x / (||x|| + 1e-8)), trans [B][3] is the translation head's
+ * output as it is, loss = PoseLoss(rot, trans) (pose_loss.py:19-28) and its gradient for
+ * dloss = 1: grad_raw [B][4] (through the normalise) and grad_trans [B][3].  rot, loss and
+ * grad_trans are bit-identical to pose6d_rownorm_fwd + pose6d_pose_loss_fwd / _bwd. */
+int pose6d_quat_head_loss(const float *raw, const float *trans, const float *gt_rot, const float *gt_trans, int64_t B,
+                          float rot_weight, float trans_weight, int32_t rot_mode, int32_t norm_mode, float *rot,
+                          float *loss, float *grad_raw, float *grad_trans, void *stream);
+
 /* ------------------------------------------------------------------------
  * Input crops -- replaces the per-sample body of LineMODDatasetRGBD.__getitem__
  * after the file reads (data/dataset_rgbd.py:104-206; dataset_rgb.py:95-145 for
