@@ -25,17 +25,11 @@
 // whenever sqrtf(new) == sqrtf(old) (same sqrt value => the old, earlier j wins).
 #include "common.h"
 
-#ifndef POSE6D_ADD_HIT
-#define POSE6D_ADD_HIT 1   // build-time: 0 = timing-only build, the minimum updates skipped (wrong results)
-#endif
-#ifndef POSE6D_ADD_SEED
-#define POSE6D_ADD_SEED 1  // build-time: 0 = never seed (the neighbour table is ignored)
-#endif
-#ifndef POSE6D_ADD_HOPS
-#define POSE6D_ADD_HOPS 2  // build-time: neighbour-table hops of the seed walk (1 = the point's own row only)
-#endif
-
 namespace {
+
+// neighbour-table hops of the seed walk (1 = the point's own row only;
+// profiles/r06_add_variants.txt)
+constexpr int kAddHops = 2;
 
 constexpr int kThreads = 256;
 constexpr int kTile = 2048;                   // gt points per LDS tile (32 KiB)
@@ -181,7 +175,7 @@ __global__ __launch_bounds__(kThreads) void add_points_kernel(
       const int k = base + tid + kThreads * i;
       if (k >= n) continue;
       int cur = k;
-      for (int h = 0; h < POSE6D_ADD_HOPS; ++h) {
+      for (int h = 0; h < kAddHops; ++h) {
         const uint16_t* row = nb + (int64_t)cur * K;
         for (int t = 0; t < K; t += 8) {
           const uint4 w = *reinterpret_cast<const uint4*>(row + t);   // 8 indices (K % 8 == 0, 16-B rows)
@@ -233,10 +227,6 @@ __global__ __launch_bounds__(kThreads) void add_points_kernel(
         for (int u = 1; u < U; ++u) m[i] = __builtin_fminf(m[i], s[u][i]);
         hit |= __ballot(SEED ? m[i] <= thr[i] : m[i] < best[i]);
       }
-#if POSE6D_ADD_HIT == 0
-      (void)m;   // timing-only build: the updates skipped (wrong results)
-      if (hit == 0x1234567ull) best[0] = 0.f;
-#else
       if (SEED && __builtin_expect(hit != 0, 0)) {
         // most of these are a point meeting its own current best (m == best <= thr):
         // only a trip wholly before the best's trip can hold a root tie that wins (a
@@ -256,7 +246,6 @@ __global__ __launch_bounds__(kThreads) void add_points_kernel(
 #pragma unroll
           for (int i = 0; i < PPT; ++i) update(i, s[u][i], j0 + jj + u);
       }
-#endif
     }
     for (; jj < jn; ++jj) {
       const float4 g = gs[jj];
@@ -480,7 +469,7 @@ extern "C" int pose6d_add_eval_nbr(const float* pred_rot, const float* pred_tran
     // the waves per SIMD) were all slower
     constexpr int kPPT = 2;
     dim3 grid(p6::ceil_div(max_npts, kThreads * kPPT), (unsigned)B);
-    if (nbr && POSE6D_ADD_SEED)
+    if (nbr)
       add_points_kernel<kPPT, 4, true><<<grid, kThreads, 0, s>>>(pred_rot, pred_trans, gt_rot, gt_trans, obj_ids,
                                                                  points, off, npts, n_slots, max_npts, min_dist,
                                                                  argmin, pt_add, nbr, K);

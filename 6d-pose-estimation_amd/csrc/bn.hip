@@ -19,16 +19,7 @@
 #include "bn_fold.h"
 #include "common.h"
 
-#ifndef POSE6D_FIN_WAVE_ROWS
-#define POSE6D_FIN_WAVE_ROWS 0     // build-time: the training finalize folds <= this many rows per channel on one wave
-                                   // (round 6: 0 -- the whole-workgroup fold is faster at every row count)
-#endif
 namespace {
-
-constexpr int kFinWaveRows = POSE6D_FIN_WAVE_ROWS;
-#ifndef POSE6D_FIN_TIMING
-#define POSE6D_FIN_TIMING 0   // timing-only builds (wrong results): 1 = finalize kernels return at entry, 2 = not launched
-#endif
 
 constexpr int kThreads = 256;
 
@@ -54,21 +45,18 @@ __device__ __forceinline__ void store_vec(T* p, const float* f) {
 }
 
 // ---------------------------------------------------------------- finalize
-// ONE launch (training): block = 256 / L channels x L lanes (L = 64 or 256 by the
-// row count); lane l folds partial rows l, l + L, ... of its channel as shifted
-// sums about K = row 0's mean:
+// ONE launch (training): one workgroup of L = 256 lanes per channel; lane l folds
+// partial rows l, l + L, ... of its channel as shifted sums about K = row 0's mean:
 //   S1 = sum_i (sum_i - n_i K),  S2 = sum_i (M2_i + n_i (mean_i - K)^2)
 // (fp64, no divisions: n_i = 32 except the last row), the lanes combine by a
-// fixed xor-shuffle tree (+ an LDS step across waves for L = 256:
-// deterministic), and mean = K + S1/N, var = (S2 - S1^2/N)/N.  The shift keeps
-// S1^2/N small against S2 (K is a mean of the same data): no E[x^2]-E[x]^2
-// cancellation.
-// lane l (of L on channel c) folds rows l, l + L, ...; after the call thread `lane == 0`
-// of the channel holds (K, s1, s2) of the whole channel (L = 256: thread 0 of the block)
-template <int L>
+// fixed xor-shuffle tree + an LDS step across waves (deterministic), and
+// mean = K + S1/N, var = (S2 - S1^2/N)/N.  The shift keeps S1^2/N small against S2
+// (K is a mean of the same data): no E[x^2]-E[x]^2 cancellation.
+// After the call thread 0 of the block holds (K, s1, s2) of the whole channel.
 __device__ __forceinline__ void bn_stats_fold(const float* __restrict__ part, int rows, int C, int64_t M, int c,
                                               double& K, double& s1, double& s2) {
   __shared__ double red[2][kThreads / 64];
+  constexpr int L = kThreads;
   const int lane = threadIdx.x % L;
   s1 = 0.0; s2 = 0.0; K = 0.0;
   if (c < C) {
@@ -104,25 +92,24 @@ __device__ __forceinline__ void bn_stats_fold(const float* __restrict__ part, in
   }
   s1 = p6::wave_sum(s1);
   s2 = p6::wave_sum(s2);
-  if constexpr (L > 64) {
-    const int w = threadIdx.x >> 6;
-    __syncthreads();   // (red reused across calls)
-    if ((threadIdx.x & 63) == 0) { red[0][w] = s1; red[1][w] = s2; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      s1 = 0.0; s2 = 0.0;
+  const int w = threadIdx.x >> 6;
+  __syncthreads();   // (red reused across calls)
+  if ((threadIdx.x & 63) == 0) { red[0][w] = s1; red[1][w] = s2; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    s1 = 0.0; s2 = 0.0;
 #pragma unroll
-      for (int i = 0; i < kThreads / 64; ++i) { s1 += red[0][i]; s2 += red[1][i]; }
-    }
+    for (int i = 0; i < kThreads / 64; ++i) { s1 += red[0][i]; s2 += red[1][i]; }
   }
 }
 
-template <int L, bool SC1 = false>
+template <bool SC1 = false>
 __device__ __forceinline__ void bn_stats_finalize_body(
     int blk, const float* __restrict__ part, int rows, int C, int64_t M, const float* __restrict__ gamma,
     const float* __restrict__ beta, float* __restrict__ rmean, float* __restrict__ rvar, int64_t* __restrict__ nbt,
     float momentum, float eps, float* __restrict__ scale, float* __restrict__ shift, float* __restrict__ smean,
     float* __restrict__ sinv) {
+  constexpr int L = kThreads;   // one workgroup per channel
   const int lane = threadIdx.x % L;
   const int c = blk * (kThreads / L) + threadIdx.x / L;
   // the per-channel parameters and running statistics the tail needs, fetched now
@@ -135,7 +122,7 @@ __device__ __forceinline__ void bn_stats_finalize_body(
     rv_c = rvar[c];
   }
   double K, s1, s2;
-  bn_stats_fold<L>(part, rows, C, M, c, K, s1, s2);
+  bn_stats_fold(part, rows, C, M, c, K, s1, s2);
   if (lane == 0 && c < C) {
     const p6::BnFoldOut o = p6::bn_fold_result(M, eps, K, s1, s2, g_c, b_c);
     const double N = (double)M;
@@ -155,41 +142,23 @@ __device__ __forceinline__ void bn_stats_finalize_body(
   }
 }
 
-template <int L>
 __global__ __launch_bounds__(kThreads) void bn_stats_finalize_kernel(
     const float* __restrict__ part, int rows, int C, int64_t M, const float* __restrict__ gamma,
     const float* __restrict__ beta, float* __restrict__ rmean, float* __restrict__ rvar, int64_t* __restrict__ nbt,
     float momentum, float eps, float* __restrict__ scale, float* __restrict__ shift, float* __restrict__ smean,
     float* __restrict__ sinv) {
-
-  if (POSE6D_FIN_TIMING == 1) return;
-  if constexpr (L == 64) {
-    // <= 512 rows: one channel per wave, the arithmetic the producing convolution's
-    // in-launch finalize shares (bn_fold.h)
-    const pose6d_bn_stats_t d{part, gamma, beta, rmean, rvar, nbt, scale, shift, smean, sinv, momentum, eps, C};
-    p6::bn_fold_wave<1>(d, [&](int64_t i) { return part[i]; }, rows, M, blockIdx.x * 4 + (threadIdx.x >> 6), 1);
-  } else {
-    bn_stats_finalize_body<L>(blockIdx.x, part, rows, C, M, gamma, beta, rmean, rvar, nbt, momentum, eps, scale,
-                              shift, smean, sinv);
-  }
+  bn_stats_finalize_body(blockIdx.x, part, rows, C, M, gamma, beta, rmean, rvar, nbt, momentum, eps, scale, shift,
+                         smean, sinv);
 }
 
 // two BatchNorms over the same output grid (a downsampling block's bn3 and its
 // downsample BN: same rows and count) in one launch, blockIdx.y selecting the BN;
-// each BN's arithmetic is bn_stats_finalize_kernel<L>'s, bit for bit
-template <int L>
+// each BN's arithmetic is bn_stats_finalize_kernel's, bit for bit
 __global__ __launch_bounds__(kThreads) void bn_stats_finalize2_kernel(pose6d_bn_stats_t a, pose6d_bn_stats_t b,
                                                                       int rows, int64_t M) {
-
-  if (POSE6D_FIN_TIMING == 1) return;
   const pose6d_bn_stats_t& d = blockIdx.y ? b : a;
-  if ((int)blockIdx.x * (kThreads / L) >= d.C) return;
-  if constexpr (L == 64) {
-    const float* part = d.partial;
-    p6::bn_fold_wave<1>(d, [&](int64_t i) { return part[i]; }, rows, M, blockIdx.x * 4 + (threadIdx.x >> 6), 1);
-    return;
-  }
-  bn_stats_finalize_body<L>(blockIdx.x, d.partial, rows, d.C, M, d.gamma, d.beta, d.running_mean, d.running_var,
+  if ((int)blockIdx.x >= d.C) return;
+  bn_stats_finalize_body(blockIdx.x, d.partial, rows, d.C, M, d.gamma, d.beta, d.running_mean, d.running_var,
                             d.num_batches, d.momentum, d.eps, d.scale, d.shift, d.save_mean, d.save_invstd);
 }
 
@@ -280,7 +249,7 @@ __global__ __launch_bounds__(kThreads) void bn_act_kernel(const T* __restrict__ 
 // pose6d_bn_finalize_act: the training finalize and bn_act_kernel's apply in ONE launch
 // (the kernel boundary between them -- a launch gap plus the apply's ramp behind a
 // ~5 us latency-bound finalize -- is what the separate launches cost).  Workgroups
-// [0, nfin) are the finalize (bn_stats_finalize_kernel<L>'s blocks, same arithmetic),
+// [0, nfin) are the finalize (bn_stats_finalize_kernel's blocks, same arithmetic),
 // each storing scale / shift write-through and then ITS ready flag (= the launch's
 // epoch).  Workgroups [nfin, ...) apply: one 64-channel column group x RPB rows each;
 // they fetch their y / residual chunks first, then one wave polls the flags of the
@@ -292,32 +261,22 @@ __global__ __launch_bounds__(kThreads) void bn_act_kernel(const T* __restrict__ 
 constexpr int kFinGroup = 64;     // channels per apply column group
 constexpr int kFinSpins = 4096;   // ~4096 x (poll + s_sleep 2) ~ 0.5 ms before the fallback
 
-template <int L>
-__device__ __forceinline__ int fin_blocks(int C) { return L == 64 ? (C + 3) / 4 : C; }
-
 // the 64 channels' scale / shift into LDS for a workgroup that gave up waiting: the
-// finalize's fold recomputed (rows <= 512: one wave per 16 channels, bn_fold.h; more
-// rows: the whole workgroup per channel, bn_stats_fold<256>)
-template <int L>
+// finalize's fold recomputed (the whole workgroup per channel, bn_stats_fold)
 __device__ void fin_fallback(const pose6d_bn_stats_t& d, int rows, int64_t M, int c0, float* sc, float* sh) {
-  if constexpr (L == 64) {
-    const int w = threadIdx.x >> 6;
-    p6::bn_fold_wave_compute(d, rows, M, c0 + 16 * w, 16, sc + 16 * w, sh + 16 * w);
-  } else {
-    for (int j = 0; j < kFinGroup; ++j) {
-      double K, s1, s2;
-      bn_stats_fold<256>(d.partial, rows, d.C, M, c0 + j, K, s1, s2);
-      if (threadIdx.x == 0 && c0 + j < d.C) {
-        const p6::BnFoldOut o = p6::bn_fold_result(M, d.eps, K, s1, s2, d.gamma[c0 + j], d.beta[c0 + j]);
-        sc[j] = o.sc;
-        sh[j] = o.sh;
-      }
+  for (int j = 0; j < kFinGroup; ++j) {
+    double K, s1, s2;
+    bn_stats_fold(d.partial, rows, d.C, M, c0 + j, K, s1, s2);
+    if (threadIdx.x == 0 && c0 + j < d.C) {
+      const p6::BnFoldOut o = p6::bn_fold_result(M, d.eps, K, s1, s2, d.gamma[c0 + j], d.beta[c0 + j]);
+      sc[j] = o.sc;
+      sh[j] = o.sh;
     }
   }
   __syncthreads();
 }
 
-template <typename T, int L>
+template <typename T>
 __global__ __launch_bounds__(kThreads) void bn_fin_act_kernel(pose6d_bn_stats_t d, int rows, int64_t M, int nfin,
                                                               const T* __restrict__ y, const T* __restrict__ res,
                                                               int relu, T* __restrict__ out,
@@ -330,16 +289,9 @@ __global__ __launch_bounds__(kThreads) void bn_fin_act_kernel(pose6d_bn_stats_t 
   const int b = blockIdx.x;
   const int C = d.C;
   if (b < nfin) {
-    // ---- finalize: bn_stats_finalize_kernel<L>'s workgroup b, scale / shift written through
-    if constexpr (L == 64) {
-      const float* part = d.partial;
-      p6::bn_fold_wave<1, p6::kBnFoldSlots, true>(d, [&](int64_t i) { return part[i]; }, rows, M,
-                                                   b * 4 + (threadIdx.x >> 6), 1);
-    } else {
-      bn_stats_finalize_body<L, true>(b, d.partial, rows, C, M, d.gamma, d.beta, d.running_mean, d.running_var,
-                                      d.num_batches, d.momentum, d.eps, d.scale, d.shift, d.save_mean,
-                                      d.save_invstd);
-    }
+    // ---- finalize: bn_stats_finalize_kernel's workgroup b, scale / shift written through
+    bn_stats_finalize_body<true>(b, d.partial, rows, C, M, d.gamma, d.beta, d.running_mean, d.running_var,
+                                 d.num_batches, d.momentum, d.eps, d.scale, d.shift, d.save_mean, d.save_invstd);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every storing wave, before the barrier
     __syncthreads();
     if (threadIdx.x == 0) p6::st_sc1(flags, b, ep);
@@ -363,7 +315,7 @@ __global__ __launch_bounds__(kThreads) void bn_fin_act_kernel(pose6d_bn_stats_t 
     if (res) load_vec(res + off, rv);
   }
   // wait for the finalize workgroups of channels [64 g, 64 g + 64)
-  constexpr int FPG = L == 64 ? kFinGroup / 4 : kFinGroup;   // finalize workgroups per group
+  constexpr int FPG = kFinGroup;   // finalize workgroups per group: one per channel
   if (threadIdx.x < 64) {
     const int lane = threadIdx.x;
     const int f = g * FPG + lane;
@@ -379,7 +331,7 @@ __global__ __launch_bounds__(kThreads) void bn_fin_act_kernel(pose6d_bn_stats_t 
   __syncthreads();
   float sc[E], sh[E];
   if (fb) {
-    fin_fallback<L>(d, rows, M, g * kFinGroup, csc, csh);
+    fin_fallback(d, rows, M, g * kFinGroup, csc, csh);
 #pragma unroll
     for (int e = 0; e < E; ++e) { sc[e] = csc[j * E + e]; sh[e] = csh[j * E + e]; }
   } else {
@@ -563,59 +515,11 @@ struct BwdFin {   // one BatchNorm's finalize operands (grid.y picks one of two)
   float *dgamma, *dbeta, *coef;
 };
 
-__global__ __launch_bounds__(kThreads) void bn_bwd_finalize_kernel(const float* __restrict__ part, int rows, int C,
-                                                                   double count, const float* __restrict__ gamma,
-                                                                   const float* __restrict__ inv,
-                                                                   float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                                   int accumulate, float* __restrict__ coef,
-                                                                   BwdFin second_v = BwdFin{}) {
-  if (blockIdx.y == 1) {   // the second BatchNorm of a dual backward
-    part = second_v.part; gamma = second_v.gamma; inv = second_v.inv;
-    dgamma = second_v.dgamma; dbeta = second_v.dbeta; coef = second_v.coef;
-  }
-  // one wave per channel: lanes read the channel's partial rows coalesced
-  // (channel-major [2][C][rows]), fp64 sums combined by a fixed xor tree
-  const int lane = threadIdx.x & 63;
-  const int c = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
-  if (c >= C) return;
-  const float* ps = part + (int64_t)c * rows;
-  const float* pq = part + ((int64_t)C + c) * rows;
-  // the tail's operands, fetched before the reduction (their round trip overlaps it)
-  float g_c = 0.f, i_c = 0.f, db0 = 0.f, dg0 = 0.f;
-  if (lane == 0) {
-    g_c = gamma[c];
-    i_c = inv[c];
-    if (accumulate) {
-      if (dbeta) db0 = dbeta[c];
-      if (dgamma) dg0 = dgamma[c];
-    }
-  }
-  double s = 0.0, q = 0.0;
-  int r = lane;
-  for (; r + 64 < rows; r += 128) {
-    const float s0 = ps[r], s1 = ps[r + 64], q0 = pq[r], q1 = pq[r + 64];
-    s += (double)s0 + (double)s1;
-    q += (double)q0 + (double)q1;
-  }
-  for (; r < rows; r += 64) {
-    s += (double)ps[r];
-    q += (double)pq[r];
-  }
-  s = p6::wave_sum(s);
-  q = p6::wave_sum(q);
-  if (lane == 0) {
-    if (dbeta) dbeta[c] = db0 + (float)s;
-    if (dgamma) dgamma[c] = dg0 + (float)q;
-    coef[c] = g_c * i_c;                    // c1
-    coef[C + c] = (float)(s / count);       // c2 = mean(dz)
-    coef[2 * C + c] = (float)(q / count);   // c3 = mean(dz * xhat)
-  }
-}
-
-// the same finalize with one WORKGROUP per channel (grid.x = C): threads over rows, fp64
-// sums combined by wave_sum and then across the four waves in order by thread 0 -- the
-// one-wave form above is latency-bound on its shuffle / lane-0 tail (the training
-// forward's finalize showed the same: tools/fin_bench.py, profiles/r06_fin_fold.txt)
+// one WORKGROUP per channel (grid.x = C): threads read the channel's partial rows coalesced
+// (channel-major [2][C][rows]), fp64 sums combined by wave_sum and then across the four
+// waves in order by thread 0 -- a one-wave-per-channel form was latency-bound on its
+// shuffle / lane-0 tail (the training forward's finalize showed the same:
+// tools/fin_bench.py, profiles/r06_fin_fold.txt)
 __global__ __launch_bounds__(kThreads) void bn_bwd_finalize_wg_kernel(const float* __restrict__ part, int rows, int C,
                                                                       double count, const float* __restrict__ gamma,
                                                                       const float* __restrict__ inv,
@@ -623,8 +527,6 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_finalize_wg_kernel(const floa
                                                                       float* __restrict__ dbeta, int accumulate,
                                                                       float* __restrict__ coef,
                                                                       BwdFin second_v = BwdFin{}) {
-
-  if (POSE6D_FIN_TIMING == 1) return;
   __shared__ double red[2][kThreads / 64];
   if (blockIdx.y == 1) {
     part = second_v.part; gamma = second_v.gamma; inv = second_v.inv;
@@ -669,19 +571,11 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_finalize_wg_kernel(const floa
   coef[2 * C + c] = (float)(q / count);
 }
 
-#ifndef POSE6D_BWD_FIN_WG
-#define POSE6D_BWD_FIN_WG 1   // build-time: 0 = the one-wave-per-channel backward finalize
-#endif
 void launch_bwd_finalize(const float* part, int rows, int C, int64_t M, const float* gamma, const float* inv,
                          float* dgamma, float* dbeta, int accumulate, float* coef, const BwdFin& b2, int ny,
                          hipStream_t s) {
-  if (POSE6D_FIN_TIMING == 2) return;
-  if (POSE6D_BWD_FIN_WG)
-    bn_bwd_finalize_wg_kernel<<<dim3(C, ny), kThreads, 0, s>>>(part, rows, C, (double)M, gamma, inv, dgamma, dbeta,
-                                                               accumulate, coef, b2);
-  else
-    bn_bwd_finalize_kernel<<<dim3(p6::ceil_div(C, kThreads / 64), ny), kThreads, 0, s>>>(
-        part, rows, C, (double)M, gamma, inv, dgamma, dbeta, accumulate, coef, b2);
+  bn_bwd_finalize_wg_kernel<<<dim3(C, ny), kThreads, 0, s>>>(part, rows, C, (double)M, gamma, inv, dgamma, dbeta,
+                                                             accumulate, coef, b2);
 }
 
 template <typename T, int MK, bool DUAL = false>
@@ -786,17 +680,9 @@ extern "C" int pose6d_bn_finalize(const float* partial, int32_t rows, int32_t C,
   (void)workspace;   // kept in the ABI; the single-launch finalize needs none
   P6_CHECK_ARG(C > 0 && (!training || (rows > 0 && count > 0)), "pose6d_bn_finalize: bad sizes");
   hipStream_t s = p6::stream_of(stream);
-  if (POSE6D_FIN_TIMING == 2 && training) return POSE6D_OK;
   if (training) {
-    if (rows > kFinWaveRows)
-      bn_stats_finalize_kernel<256><<<C, kThreads, 0, s>>>(partial, rows, C, count, gamma, beta, running_mean,
-                                                            running_var, num_batches, momentum, eps, scale, shift,
-                                                            save_mean, save_invstd);
-    else
-      bn_stats_finalize_kernel<64><<<p6::ceil_div(C, 4), kThreads, 0, s>>>(partial, rows, C, count, gamma, beta,
-                                                                          running_mean, running_var, num_batches,
-                                                                          momentum, eps, scale, shift, save_mean,
-                                                                          save_invstd);
+    bn_stats_finalize_kernel<<<C, kThreads, 0, s>>>(partial, rows, C, count, gamma, beta, running_mean, running_var,
+                                                    num_batches, momentum, eps, scale, shift, save_mean, save_invstd);
   } else {
     bn_eval_finalize_kernel<<<p6::ceil_div(C, kThreads), kThreads, 0, s>>>(gamma, beta, running_mean, running_var, C,
                                                                           eps, scale, shift, save_mean, save_invstd);
@@ -810,12 +696,8 @@ extern "C" int pose6d_bn_finalize_dual(const pose6d_bn_stats_t* a, const pose6d_
   P6_CHECK_ARG(a && b && a->C > 0 && b->C > 0 && rows > 0 && count > 0 && rows == p6::ceil_div(count, (int64_t)32),
                "pose6d_bn_finalize_dual: bad sizes");
   hipStream_t s = p6::stream_of(stream);
-  if (POSE6D_FIN_TIMING == 2) return POSE6D_OK;
   const int cmax = a->C > b->C ? a->C : b->C;
-  if (rows > kFinWaveRows)
-    bn_stats_finalize2_kernel<256><<<dim3(cmax, 2), kThreads, 0, s>>>(*a, *b, rows, count);
-  else
-    bn_stats_finalize2_kernel<64><<<dim3(p6::ceil_div(cmax, 4), 2), kThreads, 0, s>>>(*a, *b, rows, count);
+  bn_stats_finalize2_kernel<<<dim3(cmax, 2), kThreads, 0, s>>>(*a, *b, rows, count);
   P6_LAUNCH_CHECK();
   return POSE6D_OK;
 }
@@ -837,9 +719,11 @@ extern "C" int pose6d_bn_act_fwd_mask(int32_t dtype, const void* y, const float*
   return POSE6D_OK;
 }
 
-// ready flags one pose6d_bn_finalize_act launch needs (int32, zeroed once by the caller)
+// ready flags one pose6d_bn_finalize_act launch needs (int32, zeroed once by the caller):
+// one per finalize workgroup, i.e. per channel
 extern "C" int32_t pose6d_bn_finalize_act_flags(int32_t rows, int32_t C) {
-  return rows > kFinWaveRows ? C : (C + 3) / 4;
+  (void)rows;
+  return C;
 }
 
 extern "C" int pose6d_bn_finalize_act(int32_t dtype, const pose6d_bn_stats_t* bn, int32_t rows, int64_t count,
@@ -859,12 +743,8 @@ extern "C" int pose6d_bn_finalize_act(int32_t dtype, const pose6d_bn_stats_t* bn
     constexpr int RPB = kThreads / (kFinGroup / V<TT>::E);
     const int64_t napp = (int64_t)(C / kFinGroup) * p6::ceil_div(count, RPB);
     const unsigned grid = (unsigned)(nfin + napp);
-    if (rows > kFinWaveRows)
-      bn_fin_act_kernel<TT, 256><<<grid, kThreads, 0, s>>>(*bn, rows, count, nfin, (const TT*)y, (const TT*)res, relu,
-                                                           (TT*)out, relu_mask, flags, epoch);
-    else
-      bn_fin_act_kernel<TT, 64><<<grid, kThreads, 0, s>>>(*bn, rows, count, nfin, (const TT*)y, (const TT*)res, relu,
-                                                          (TT*)out, relu_mask, flags, epoch);
+    bn_fin_act_kernel<TT><<<grid, kThreads, 0, s>>>(*bn, rows, count, nfin, (const TT*)y, (const TT*)res, relu,
+                                                    (TT*)out, relu_mask, flags, epoch);
   };
   if (dtype == POSE6D_DT_BF16) go((bf16*)nullptr);
   else go((float*)nullptr);

@@ -103,4 +103,9 @@ inline hipStream_t stream_of(void* s) { return reinterpret_cast<hipStream_t>(s);
 
 __host__ __device__ inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// an override field of a pose6d_tuning_t, or the default (-1 / no struct)
+inline int tuned(const pose6d_tuning_t* t, int32_t pose6d_tuning_t::*f, int dflt) {
+  return (t && t->*f >= 0) ? (int)(t->*f) : dflt;
+}
+
 }  // namespace p6

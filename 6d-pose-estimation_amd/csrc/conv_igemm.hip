@@ -807,11 +807,6 @@ __device__ __forceinline__ void mma_frag(f32x4& acc, const u32x4& a, const u32x4
   }
 }
 
-#ifndef POSE6D_PAIRED_FRAGS
-#define POSE6D_PAIRED_FRAGS 1
-#endif
-constexpr bool kPairedFrags = POSE6D_PAIRED_FRAGS;
-
 // Element geometry of the LDS-DMA path: a 16-byte chunk holds CH elements, a K-step
 // (one 128-byte LDS row per GEMM row) KS = 8 CH: 64 bf16 or 32 fp32.  bf16 feeds
 // v_mfma_f32_16x16x32_bf16 (one per 16x16 tile and k-half); fp32 feeds the exact
@@ -822,14 +817,7 @@ template <typename T> struct LK { static constexpr int CH = 16 / (int)sizeof(T),
 // one workgroup's work; `bid_in` = its index in this conv's sub-grid (the whole grid,
 // or the leading part of a fused backward launch), `smem` = the kernel's dynamic LDS
 // PRE: a workgroup with at most two K-steps fetches its epilogue's global operands
-// (epi_prefetch) right after issuing its operand DMA (build-time switch for A/B
-// timing: -DPOSE6D_EPI_PRE=0 builds the fetch-after-the-loop form)
-#ifndef POSE6D_EPI_PRE
-#define POSE6D_EPI_PRE 1
-#endif
-#ifndef POSE6D_S2_ROTATE
-#define POSE6D_S2_ROTATE 1   // build-time (A/B): 0 = the fixed class order (profiles/r05rot_s2_class_order_ab.txt)
-#endif
+// (epi_prefetch) right after issuing its operand DMA (profiles/r03t_epi_prefetch_ab.txt)
 template <typename T, int BM, int BN, int MODE, int S, bool ACT = false, int NW = 4, bool BNR = false,
           bool PRE = false>
 __device__ __forceinline__ void conv_lds_body(char* smem, int bid_in, const T* __restrict__ src,
@@ -875,15 +863,12 @@ __device__ __forceinline__ void conv_lds_body(char* smem, int bid_in, const T* _
     if (g.s2one) {
       cls = g.s2one - 1;
     } else {
-#if POSE6D_S2_ROTATE
       // the four classes of tile t are logical ids 4t .. 4t+3 (one XCD, one L2), in an
       // order that rotates with t: the dispatcher deals an XCD's workgroups out to its
       // shader engines in turn, so a fixed order would give each engine one class (the
-      // 4-tap class's engine doing 4/9 of the work; a 1x1's tap class on one engine)
+      // 4-tap class's engine doing 4/9 of the work; a 1x1's tap class on one engine;
+      // profiles/r05rot_s2_class_order_ab.txt)
       cls = 3 - ((bid + (bid >> 2)) & 3);
-#else
-      cls = 3 - (bid & 3);
-#endif
       bid >>= 2;
     }
     py = cls >> 1; px = cls & 1;
@@ -1016,7 +1001,7 @@ __device__ __forceinline__ void conv_lds_body(char* smem, int bid_in, const T* _
   };
 
   // one stage's DMA as (source, LDS destination) pairs, then the tap walk advanced;
-  // issue() fires them back to back, the interleaved compute (POSE6D_ILV) one per MFMA
+  // issue() fires them back to back
   const T* dsrc[LOADS];
   char* ddst[LOADS];
   auto prep = [&](int buf) {
@@ -1107,60 +1092,9 @@ __device__ __forceinline__ void conv_lds_body(char* smem, int bid_in, const T* _
   const unsigned ring_base = lds_addr(smem);
   // mid(): issued between the fragment reads and their wait, so the next stage's
   // LDS-DMA issue (tens of cycles per instruction) overlaps the LDS read latency
-  // POSE6D_ILV: the next stage's DMA instructions issued one after each first-k-half
-  // MFMA instead of as one burst before them (a DMA wave-instruction costs the wave
-  // ~60-185 issue cycles, an MFMA 16 of pipe time: interleaved, the issue cost hides
-  // behind the matrix pipe)
-  auto compute_ilv = [&](int buf, bool has, auto& acc) {
-    const unsigned slot = ring_base + buf * STAGE;
-    constexpr int NM = TM * TN;   // MFMAs per k-half
-    constexpr int GAP = NM / LOADS > 0 ? NM / LOADS : 1;
-    if constexpr (TM + TN == 4 && kPairedFrags) {
-      unsigned addr[2][4];
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) addr[kk][r] = slot + frag_off[kk][r];
-      u32x4 f[2][4];
-      lds_issue_frags8(f, addr);
-      lds_wait_first(f[0]);
-#pragma unroll
-      for (int q = 0; q < NM; ++q) {
-        mma_frag<T>(acc[q / TN][q % TN], f[0][q / TN], f[0][TM + q % TN]);
-        if (q % GAP == GAP - 1 && q / GAP < LOADS && has) glds16(dsrc[q / GAP], ddst[q / GAP]);
-      }
-#pragma unroll
-      for (int q = NM / GAP; q < LOADS; ++q)
-        if (has) glds16(dsrc[q], ddst[q]);
-      lds_wait_all(f[1]);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) mma_frag<T>(acc[i][j], f[1][i], f[1][TM + j]);
-      return;
-    }
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      unsigned addr[TM + TN];
-#pragma unroll
-      for (int r = 0; r < TM + TN; ++r) addr[r] = slot + frag_off[kk][r];
-      u32x4 f[TM + TN];
-      lds_read_frags<TM + TN>(f, addr);
-#pragma unroll
-      for (int q = 0; q < NM; ++q) {
-        mma_frag<T>(acc[q / TN][q % TN], f[q / TN], f[TM + q % TN]);
-        if (kk == 0 && q % GAP == GAP - 1 && q / GAP < LOADS && has) glds16(dsrc[q / GAP], ddst[q / GAP]);
-      }
-      if (kk == 0) {
-#pragma unroll
-        for (int q = NM / GAP; q < LOADS; ++q)
-          if (has) glds16(dsrc[q], ddst[q]);
-      }
-    }
-  };
   auto compute = [&](int buf, auto&& mid, auto& acc) {
     const unsigned slot = ring_base + buf * STAGE;
-    if constexpr (TM + TN == 4 && kPairedFrags) {
+    if constexpr (TM + TN == 4) {
       unsigned addr[2][4];
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk)
@@ -1201,7 +1135,7 @@ __device__ __forceinline__ void conv_lds_body(char* smem, int bid_in, const T* _
   // waits (which count DMA only) over-wait it on the first step -- correct, and with
   // one or two K-steps the two sets of loads are in flight together
   EpiPre<T, BM, BN, NW, BNR> pre;
-  const bool early = POSE6D_EPI_PRE && PRE && !DUAL && nk <= 2;
+  const bool early = PRE && !DUAL && nk <= 2;
   if (early) epi_prefetch<T, BM, BN, ACT ? 1 : 0, NW, BNR>(pre, g, res, m0, n0, cls);
   int cur = 0, wbuf = S - 1;
   for (int kt = 0; kt < nk; ++kt) {
@@ -1223,16 +1157,7 @@ __device__ __forceinline__ void conv_lds_body(char* smem, int bid_in, const T* _
           }
       }
     }
-#ifndef POSE6D_ILV
-#define POSE6D_ILV 0
-#endif
-    if constexpr (POSE6D_ILV && !DUAL) {
-      const bool has = kt + S - 1 < nk;
-      if (has) prep(wbuf);
-      compute_ilv(cur, has, acc);
-    } else {
-      compute(cur, mid, acc);
-    }
+    compute(cur, mid, acc);
     cur = cur == S - 1 ? 0 : cur + 1;
     wbuf = wbuf == S - 1 ? 0 : wbuf + 1;
   }
@@ -1271,10 +1196,9 @@ __global__ __launch_bounds__(64 * NW) void conv_lds_kernel(const T* __restrict__
 // gradient workgroups they were the launch's tail.
 // T = float: the same launch for the reference-precision (fp32) step -- the fp32
 // LDS-DMA data gradient and the fp32 LDS-DMA weight gradient (wgrad_body.h).
-#ifndef POSE6D_BWD_F32_MS
-#define POSE6D_BWD_F32_MS 32   // build-time (A/B): pixels per fp32 weight-gradient stage in the fused launch
-#endif
-constexpr int kBwdF32MS = POSE6D_BWD_F32_MS;
+// pixels per fp32 64x64 weight-gradient stage in the fused launch: 32 (with fused_ds's
+// 3-slot data-gradient ring) fits three workgroups per CU (profiles/r05f32r_bwd_ring_ab.txt)
+constexpr int kBwdF32MS = 32;
 // WBT (fp32 only): the weight-gradient tile, 64 or 128 (the wider KxK convs' plans: 128x128
 // on 32-pixel stages, conv_wgrad_lds_body_f32)
 template <int DMODE, int DS, int WS, typename T = bf16, int WBT = 64>
@@ -1544,25 +1468,25 @@ bool fast_ok(int dtype, int mode, const Geom& g) {
 // (tools/conv_bench.py) but lost in the step, so bf16 never picks it.  fp32
 // (MFMA-bound: 4x the MFMAs per byte) takes 128x128 on long K at about one
 // workgroup per CU (profiles/r02_conv_tiles.txt).
-#ifndef POSE6D_TILE4_MIN_K
-#define POSE6D_TILE4_MIN_K 128   // build-time (A/B): the bf16 128x128 tile's minimum K (round 4:
-                                 // 256 -> 128 moved layer2's 128 -> 512 convs onto it, step 4.608 -> 4.601 ms)
-#endif
+// the bf16 128x128 tile's minimum K: 128 puts layer2's 128 -> 512 convs on it
+// (profiles/r04_tile4_k128_ab.txt)
+constexpr int kTile4MinK = 128;
 int pick_tile_fast(int dtype, int64_t M, int N, int K) {
   const int64_t wg4 = p6::ceil_div(M, 128) * (int64_t)p6::ceil_div(N, 128);
-#ifndef POSE6D_F32_TILE_RULE
-#define POSE6D_F32_TILE_RULE 0   // build-time (A/B): 1 = 128x128 from K >= 256 on >= 96 tiles, 2 = from K >= 128, N >= 128
-#endif
-  if (dtype == POSE6D_DT_F32 && POSE6D_F32_TILE_RULE == 1) return (K >= 256 && N >= 128 && wg4 >= 96) ? 4 : 3;
-  if (dtype == POSE6D_DT_F32 && POSE6D_F32_TILE_RULE == 2) return (K >= 128 && N >= 128) ? 4 : 3;
   if (dtype == POSE6D_DT_F32) return (K >= 512 && N >= 128 && wg4 >= 192 && wg4 < 384) ? 4 : 3;
-  return (N >= 128 && K >= POSE6D_TILE4_MIN_K && wg4 >= 384) ? 4 : 3;
+  return (N >= 128 && K >= kTile4MinK && wg4 >= 384) ? 4 : 3;
 }
 
-// an override field of a pose6d_tuning_t, or the default (-1 / no struct)
-int tune(const pose6d_tuning_t* t, int32_t pose6d_tuning_t::*f, int dflt) {
-  return (t && t->*f >= 0) ? (int)(t->*f) : dflt;
-}
+using p6::tuned;
+
+// a tile code's extent: 0 = 128x128, 1 = 128x64, 3 = 64x64 (4 waves); 4 = 128x128,
+// 5 = 128x64 (8 waves)
+struct TileDims {
+  bool rows128, cols128;
+  int bm() const { return rows128 ? 128 : 64; }
+  int bn() const { return cols128 ? 128 : 64; }
+};
+TileDims tile_dims(int tile) { return {tile <= 1 || tile == 4 || tile == 5, tile == 0 || tile == 4}; }
 
 struct Plan {
   bool fast;
@@ -1587,9 +1511,9 @@ bool s2_ok(const Geom& g) {
 // and 95.2 -> 83.7 us (profiles/r04_f32_conv_sweep.txt).  Everywhere else the merge (write-through partial stores, the
 // arrival atomic, the partial reads: ~3-5 us on the last arriver's critical path)
 // costs more than the shorter K loop saves (profiles/r04_splitk_sweep.txt).
-#ifndef POSE6D_SPLITK_SMALL_TILES
-#define POSE6D_SPLITK_SMALL_TILES 64   // build-time (A/B): 0 = the batch-32 rule only
-#endif
+// grids of at most this many 64x64 tiles with >= 16 K-steps split K four ways
+// (profiles/r06_b1_splitk.txt)
+constexpr int kSplitkSmallTiles = 64;
 int default_splits(int dtype, int mode, const Geom& g, bool fused) {
   if (fused || !(mode == kGemm || mode == kFwd || mode == kDgrad)) return 1;
   (void)dtype;
@@ -1599,7 +1523,7 @@ int default_splits(int dtype, int mode, const Geom& g, bool fused) {
   // small grids (batch 1-2: at most a quarter of the CUs busy) with >= 16 K-steps: four
   // shorter K walks per tile (B = 1 eval forwards 7.7 -> 7.1 us on 14x14 1024->256, 14.4 ->
   // 10.6 us on layer4's 3x3; profiles/r06_b1_splitk.txt); no batch-32 conv has <= 64 tiles
-  if (nk >= 16 && tiles64 <= POSE6D_SPLITK_SMALL_TILES) return 4;
+  if (nk >= 16 && tiles64 <= kSplitkSmallTiles) return 4;
   if (nk >= 32 && tiles64 <= 256) return 2;
   return 1;
 }
@@ -1608,98 +1532,69 @@ int default_splits(int dtype, int mode, const Geom& g, bool fused) {
 Plan choose(int dtype, int mode, const Geom& g, bool fused = false, const pose6d_tuning_t* tn = nullptr,
             bool fwd = false) {
   Plan p{};
-  p.fast = fast_ok(dtype, mode, g) && tune(tn, &pose6d_tuning_t::conv_base, 0) == 0;
+  p.fast = fast_ok(dtype, mode, g) && tuned(tn, &pose6d_tuning_t::conv_base, 0) == 0;
   p.mode = mode;
   p.g = g;
   if (!p.fast) {
-    p.tile = tune(tn, &pose6d_tuning_t::conv_tile, pick_tile(g.M, g.Ncols));
+    p.tile = tuned(tn, &pose6d_tuning_t::conv_tile, pick_tile(g.M, g.Ncols));
     if (p.tile > 3) p.tile = 3;
     return p;
   }
-  if (mode == kDgrad && s2_ok(g) && tune(tn, &pose6d_tuning_t::conv_s2, 1)) {
+  if (mode == kDgrad && s2_ok(g) && tuned(tn, &pose6d_tuning_t::conv_s2, 1)) {
     p.mode = kDgradS2;
     p.g.M = g.M / 4;
     p.g.RH = g.RH / 2;
     p.g.RW = g.RW / 2;
   }
-  // build-time forward-plan overrides (A/B variant builds only: tools/build_variant.sh);
-  // they apply to bf16 forward convs with M <= POSE6D_FWD_OVR_MAXM
-#ifndef POSE6D_FWD_OVR_MAXM
-#define POSE6D_FWD_OVR_MAXM 0
-#endif
-#ifndef POSE6D_FWD_TILE
-#define POSE6D_FWD_TILE -1
-#endif
-#ifndef POSE6D_FWD_STAGES
-#define POSE6D_FWD_STAGES 0
-#endif
-  const bool ovr = fwd && dtype == POSE6D_DT_BF16 && p.g.M <= POSE6D_FWD_OVR_MAXM;
   int dflt_tile = pick_tile_fast(dtype, p.g.M, g.Ncols, g.K);
   // long-K 1x1 forwards on the small grids (layer3 / layer4 at batch 32, M <= 6272): 8-wave
   // tiles on a 4-slot ring -- 128x128 where that still gives >= 96 workgroups, else
   // 128x64.  In-graph eval times (profiles/r05b_eval_variants.txt): 1024->256 16.0 ->
   // 11.0 us, 1024->512 18.9 -> 15.9, 1024->2048/s2 17.5 -> 15.2, 2048->512 12.9 -> 12.3
-#ifndef POSE6D_LONG1X1
-#define POSE6D_LONG1X1 1   // build-time (A/B): 0 = the round-4 tile / ring rules for these convs
-#endif
-  const bool long1x1 = POSE6D_LONG1X1 && fwd && dtype == POSE6D_DT_BF16 && g.KH == 1 && g.KW == 1 && g.K >= 1024 &&
-                       p.g.M <= 6272;
+  const bool long1x1 = fwd && dtype == POSE6D_DT_BF16 && g.KH == 1 && g.KW == 1 && g.K >= 1024 && p.g.M <= 6272;
   if (long1x1) {
     const int64_t wg4 = (int64_t)p6::ceil_div(p.g.M, 128) * p6::ceil_div(g.Ncols, 128);
     dflt_tile = (g.Ncols >= 512 && wg4 >= 96) ? 4 : 5;
   }
-  if (ovr && POSE6D_FWD_TILE >= 0) dflt_tile = POSE6D_FWD_TILE;
   // fp32 KxK stride-2 data gradients (four parity classes of 1-4 taps): 64x64 tiles on a
   // 4-slot ring -- graph-timed 56x56 128->128 114.6 -> 94.1, 28x28 256->256 97.1 -> 92.0,
   // 14x14 512->512 165.0 -> 111.7 us (profiles/r05s2st_f32_s2_dgrad_plan.txt)
-#ifndef POSE6D_F32_S2_PLAN
-#define POSE6D_F32_S2_PLAN 1   // build-time (A/B): 0 = the generic tile / ring rules
-#endif
-  const bool f32s2 = POSE6D_F32_S2_PLAN && dtype == POSE6D_DT_F32 && p.mode == kDgradS2 && !fused &&
-                     (g.KH > 1 || g.KW > 1);
+  const bool f32s2 = dtype == POSE6D_DT_F32 && p.mode == kDgradS2 && !fused && (g.KH > 1 || g.KW > 1);
   if (f32s2) dflt_tile = 3;
-  p.tile = (fused || mode == kGemmDual) ? 3 : tune(tn, &pose6d_tuning_t::conv_tile, dflt_tile);
+  p.tile = (fused || mode == kGemmDual) ? 3 : tuned(tn, &pose6d_tuning_t::conv_tile, dflt_tile);
   if (p.tile == 2 || p.tile < 0 || p.tile > 5) p.tile = 3;   // no 64x128 instance on the fast path
   // two slots (32 KiB at 64x64) keep several workgroups per CU resident, which hides
   // the DMA latency better than a deeper ring; only long-K grids that leave CUs
   // idle (one wave of workgroups) take a 4-deep ring
-  // tiles: 0 = 128x128, 1 = 128x64, 3 = 64x64 (4 waves); 4 = 128x128, 5 = 128x64 (8 waves)
-  const bool rows128 = p.tile <= 1 || p.tile == 4 || p.tile == 5;
-  const bool cols128 = p.tile == 0 || p.tile == 4;
-  const int64_t grid = (int64_t)p6::ceil_div(p.g.M, rows128 ? 128 : 64) * p6::ceil_div(g.Ncols, cols128 ? 128 : 64) *
-                       (p.mode == kDgradS2 ? 4 : 1);
-  int dflt = (fast_nk(p.mode, p.g, dtype == POSE6D_DT_BF16 ? 64 : 32) > 24 && grid <= 512) ? 4 : 2;
+  const TileDims td = tile_dims(p.tile);
+  const int64_t tiles = (int64_t)p6::ceil_div(p.g.M, td.bm()) * p6::ceil_div(g.Ncols, td.bn());
+  const int64_t grid = tiles * (p.mode == kDgradS2 ? 4 : 1);
+  const int nk = fast_nk(p.mode, p.g, dtype == POSE6D_DT_BF16 ? 64 : 32);
+  int dflt = (nk > 24 && grid <= 512) ? 4 : 2;
   // fp32 forward (MFMA-bound: 4 exact 16x16x4 MFMAs per 16-byte chunk): 3 slots for
   // 1x1 filters, 2 for the rest (tools/conv_bench.py --graph --dtype f32 sweep, round 2)
   if (dtype == POSE6D_DT_F32 && (p.mode == kGemm || p.mode == kFwd)) dflt = (g.KH == 1 && g.KW == 1) ? 3 : 2;
   if (long1x1 || f32s2) dflt = 4;
-  if (ovr && POSE6D_FWD_STAGES > 0) dflt = POSE6D_FWD_STAGES;
-  p.stages = tune(tn, &pose6d_tuning_t::conv_stages, dflt);
+  p.stages = tuned(tn, &pose6d_tuning_t::conv_stages, dflt);
   if (p.stages < 2) p.stages = 2;
   if (p.stages > 6) p.stages = 6;
   if (p.stages == 5) p.stages = 4;
-  if (cols128 && rows128 && p.stages > 4) p.stages = 4;   // 6 x 32 KiB exceeds the 160 KiB LDS
+  if (td.cols128 && td.rows128 && p.stages > 4) p.stages = 4;   // 6 x 32 KiB exceeds the 160 KiB LDS
   if (fused && p.stages == 3) p.stages = 4;   // the fused backward instantiates 2- and 4-slot data gradients
   // forwards split by default; data gradients only under an explicit tuning (tests, tools):
   // the backward entry points take no split-K workspace, and the fused and separate data
   // gradients stay one plan (one summation order)
-  p.g.splits = tune(tn, &pose6d_tuning_t::conv_splitk, fwd ? default_splits(dtype, p.mode, p.g, fused) : 1);
+  p.g.splits = tuned(tn, &pose6d_tuning_t::conv_splitk, fwd ? default_splits(dtype, p.mode, p.g, fused) : 1);
   if (fused || !(p.mode == kGemm || p.mode == kFwd || p.mode == kDgrad) || p.g.splits < 1) p.g.splits = 1;
-  {
-    const int64_t tiles = (int64_t)p6::ceil_div(p.g.M, rows128 ? 128 : 64) * p6::ceil_div(g.Ncols, cols128 ? 128 : 64);
-    const int nk = fast_nk(p.mode, p.g, dtype == POSE6D_DT_BF16 ? 64 : 32);
-    if (tiles > kSkMaxTiles) p.g.splits = 1;
-    if (p.g.splits > nk) p.g.splits = nk > 0 ? nk : 1;
-  }
+  if (tiles > kSkMaxTiles) p.g.splits = 1;
+  if (p.g.splits > nk) p.g.splits = nk > 0 ? nk : 1;
   // split-K plans keep their long-K ring depth (the sweep's fastest: 4 slots) unless tuned
-  if (p.g.splits > 1 && tune(tn, &pose6d_tuning_t::conv_stages, -1) < 0 && p.stages < 4 && !(cols128 && rows128))
+  if (p.g.splits > 1 && tuned(tn, &pose6d_tuning_t::conv_stages, -1) < 0 && p.stages < 4 &&
+      !(td.cols128 && td.rows128))
     p.stages = 4;
   return p;
 }
 
-#ifndef POSE6D_PATCH
-#define POSE6D_PATCH 1   // build-time (A/B): 0 = 3x3 forwards always on the implicit GEMM
-#endif
 // 2 ring slots: deeper rings measured slower (graph-timed, profiles/r05d_patch_sweep.txt:
 // 56x56 64->64 17.8 / 23.5 / 25.1 us at 2 / 3 / 6 slots)
 constexpr int kPatchStages = 2;
@@ -1708,7 +1603,7 @@ constexpr int kPatchStages = 2;
 // (tile / ring / kernel / split-K) or turns it off (conv_patch = 0)
 bool patch_eligible(int dtype, int mode, const Geom& g, const float* stats, const pose6d_tuning_t* tn,
                     PatchPlan* pp) {
-  if (!POSE6D_PATCH || dtype != POSE6D_DT_BF16 || mode != kFwd || stats != nullptr) return false;
+  if (dtype != POSE6D_DT_BF16 || mode != kFwd || stats != nullptr) return false;
   if (g.KH != 3 || g.KW != 3 || g.stride != 1 || g.pad != 1 || g.SH != g.RH || g.SW != g.RW) return false;
   if (g.SC % 64 != 0 || g.Ncols % kPatchBN != 0 || g.Kpad != g.K || g.act_rscale != nullptr) return false;
   if (tn) {
@@ -1731,9 +1626,7 @@ bool patch_eligible(int dtype, int mode, const Geom& g, const float* stats, cons
 // bytes of split-K workspace a plan needs (0: it does not split K)
 int64_t splitk_need(const Plan& p) {
   if (!p.fast || p.g.splits <= 1) return 0;
-  const bool rows128 = p.tile <= 1 || p.tile == 4 || p.tile == 5;
-  const bool cols128 = p.tile == 0 || p.tile == 4;
-  const int bm = rows128 ? 128 : 64, bn = cols128 ? 128 : 64;
+  const int bm = tile_dims(p.tile).bm(), bn = tile_dims(p.tile).bn();
   const int64_t tiles = (int64_t)p6::ceil_div(p.g.M, bm) * p6::ceil_div(p.g.Ncols, bn);
   return kSkCntBytes + tiles * p.g.splits * bm * bn * 4;
 }
@@ -2002,6 +1895,11 @@ extern "C" int pose6d_conv2d_dgrad_tuned(int32_t dtype, const void* dy, const vo
 
 namespace {
 
+// dispatch-order rule of the fused launch: an fp32 64-pixel weight-gradient stage is
+// twice the MACs of a 32-channel data-gradient K-step, so it counts double (28x28
+// 128->512 fp32: 79.5 -> 72.5 us with the weight gradient first, profiles/r04_bwd_plan_sweep.txt)
+constexpr int kBwdWstepF32 = 2;
+
 template <int DMODE, int DS, int WS, typename T = bf16, int WBT = 64>
 int launch_bwd(const Geom& gd0, const p6::WGeom& gw, const void* dy, const void* wt, const void* dres, void* dx,
                const void* x, float* ws, const ReduceJob& rj, hipStream_t s, int order) {
@@ -2020,19 +1918,10 @@ int launch_bwd(const Geom& gd0, const p6::WGeom& gw, const void* dy, const void*
   int lds = ring_d > epi ? ring_d : epi;
   lds = lds > ring_w ? lds : ring_w;
   if (sizeof(T) == 4 && WBT == 128 && lds < acc_stage_bytes<128, 128>()) lds = acc_stage_bytes<128, 128>();
-  // longest workgroups first: the weight gradient's K-steps per split against the
-  // data gradient's K-steps per tile.  fp32: a 64-pixel weight-gradient stage is twice
-  // the MACs of a 32-channel data-gradient K-step (28x28 128->512 fp32: 79.5 -> 72.5 us
-  // with the weight gradient first, profiles/r04_bwd_plan_sweep.txt)
-#ifndef POSE6D_BWD_WSTEP_F32
-#define POSE6D_BWD_WSTEP_F32 2   // build-time (A/B): 1 = compare stages and K-steps 1:1 for fp32 too
-#endif
-  constexpr int WSTEP = sizeof(T) == 4 ? POSE6D_BWD_WSTEP_F32 : 1;
-#ifndef POSE6D_BWD_ORDER
-#define POSE6D_BWD_ORDER 1   // build-time (A/B): 0 = the data gradient always first, 2 = the weight gradient
-#endif
-  const int wfirst = order >= 0 ? order
-                                : (POSE6D_BWD_ORDER == 2 || (POSE6D_BWD_ORDER && WSTEP * p6::ceil_div(gw.mps, 64) >= nk));
+  // longest workgroups first: the weight gradient goes first when its stages per split
+  // are at least the data gradient's K-steps per tile (fp32 stages weighted kBwdWstepF32)
+  constexpr int WSTEP = sizeof(T) == 4 ? kBwdWstepF32 : 1;
+  const int wfirst = order >= 0 ? order : (WSTEP * p6::ceil_div(gw.mps, 64) >= nk);
   const int grid = wfirst ? ((nw + 7) & ~7) + nd + rj.nblk : nd_pad + nw + rj.nblk;
   conv_bwd_kernel<DMODE, DS, WS, T, WBT><<<grid, kThreads, lds, s>>>(
       (const T*)dy, (const T*)wt, (const T*)dres, (T*)dx, gd, nd, nd_pad, wfirst, (const T*)x, ws, gw, rj);
@@ -2060,10 +1949,7 @@ int launch_bwd8(const Geom& gd0, const p6::WGeom& gw, const void* dy, const void
   int lds = ring_d > epi ? ring_d : epi;
   lds = lds > ring_w ? lds : ring_w;
   lds = lds > acc_stage_bytes<128, 128>() ? lds : acc_stage_bytes<128, 128>();
-#ifndef POSE6D_BWD8_ORDER
-#define POSE6D_BWD8_ORDER POSE6D_BWD_ORDER   // build-time (A/B): the 8-wave launch's order rule (as POSE6D_BWD_ORDER)
-#endif
-  const int wfirst = order >= 0 ? order : (POSE6D_BWD8_ORDER == 2 || (POSE6D_BWD8_ORDER && p6::ceil_div(gw.mps, 64) >= nk));
+  const int wfirst = order >= 0 ? order : (p6::ceil_div(gw.mps, 64) >= nk);   // the rule of launch_bwd
   const int grid = wfirst ? ((nw + 7) & ~7) + nd + rj.nblk : nd_pad + nw + rj.nblk;
   conv_bwd8_kernel<DMODE, DS, WS><<<grid, 2 * kThreads, lds, s>>>(
       (const bf16*)dy, (const bf16*)wt, (const bf16*)dres, (bf16*)dx, gd, nd, nd_pad, wfirst, (const bf16*)x, ws, gw,
@@ -2076,9 +1962,6 @@ template <int DMODE>
 int launch_bwd8_mode(int ds, int ws_stages, const Geom& gd, const p6::WGeom& gw, const void* dy, const void* wt,
                      const void* dres, void* dx, const void* x, float* ws, const ReduceJob& rj, hipStream_t s,
                      int order) {
-#ifdef POSE6D_BWD8_DS   // build-time (A/B): force the 8-wave fused launch's data-gradient ring depth
-  ds = POSE6D_BWD8_DS;
-#endif
   if (ws_stages >= 3)
     return ds == 2 ? launch_bwd8<DMODE, 2, 3>(gd, gw, dy, wt, dres, dx, x, ws, rj, s, order)
                    : launch_bwd8<DMODE, 4, 3>(gd, gw, dy, wt, dres, dx, x, ws, rj, s, order);
@@ -2091,12 +1974,11 @@ int launch_bwd8_mode(int ds, int ws_stages, const Geom& gd, const p6::WGeom& gw,
 // fits 48 KiB of LDS and three workgroups per CU (its VGPR budget allows three) -- the
 // fp32 step 12.19 -> 11.94 ms against 4 slots and 64-pixel stages (64 KiB, two per CU;
 // profiles/r05f32r_bwd_ring_ab.txt)
-#ifndef POSE6D_BWD_BF16_DS4
-#define POSE6D_BWD_BF16_DS4 4   // build-time (A/B): the bf16 fused data-gradient ring for 4-slot plans
-#endif
+// the bf16 fused data-gradient ring for 4-slot plans stays 4 (profiles/r05bfr_bf16_bwd_ring_ab.txt)
+constexpr int kBwdBf16DS4 = 4;
 int fused_ds(int dtype, int stages) {
   if (stages <= 2) return stages;
-  return dtype == POSE6D_DT_F32 ? 3 : POSE6D_BWD_BF16_DS4;
+  return dtype == POSE6D_DT_F32 ? 3 : kBwdBf16DS4;
 }
 
 template <int DMODE>
@@ -2105,15 +1987,15 @@ int launch_bwd_mode(int dtype, int ds, const Geom& gd, const p6::WGeom& gw, cons
                     int order, int wbt = 64) {
   if (dtype == POSE6D_DT_F32 && wbt == 128)
     return fused_ds(dtype, ds) == 2
-               ? launch_bwd<DMODE, 2, POSE6D_WGRAD_STAGES_F32, float, 128>(gd, gw, dy, wt, dres, dx, x, ws, rj, s, order)
-               : launch_bwd<DMODE, 3, POSE6D_WGRAD_STAGES_F32, float, 128>(gd, gw, dy, wt, dres, dx, x, ws, rj, s,
+               ? launch_bwd<DMODE, 2, p6::kWgradStagesF32, float, 128>(gd, gw, dy, wt, dres, dx, x, ws, rj, s, order)
+               : launch_bwd<DMODE, 3, p6::kWgradStagesF32, float, 128>(gd, gw, dy, wt, dres, dx, x, ws, rj, s,
                                                                           order);
   if (dtype == POSE6D_DT_F32)
     return fused_ds(dtype, ds) == 2
-               ? launch_bwd<DMODE, 2, POSE6D_WGRAD_STAGES_F32, float>(gd, gw, dy, wt, dres, dx, x, ws, rj, s, order)
-               : launch_bwd<DMODE, 3, POSE6D_WGRAD_STAGES_F32, float>(gd, gw, dy, wt, dres, dx, x, ws, rj, s, order);
-  return ds == 2 ? launch_bwd<DMODE, 2, POSE6D_WGRAD_STAGES>(gd, gw, dy, wt, dres, dx, x, ws, rj, s, order)
-                 : launch_bwd<DMODE, POSE6D_BWD_BF16_DS4, POSE6D_WGRAD_STAGES>(gd, gw, dy, wt, dres, dx, x, ws, rj, s,
+               ? launch_bwd<DMODE, 2, p6::kWgradStagesF32, float>(gd, gw, dy, wt, dres, dx, x, ws, rj, s, order)
+               : launch_bwd<DMODE, 3, p6::kWgradStagesF32, float>(gd, gw, dy, wt, dres, dx, x, ws, rj, s, order);
+  return ds == 2 ? launch_bwd<DMODE, 2, p6::kWgradStages>(gd, gw, dy, wt, dres, dx, x, ws, rj, s, order)
+                 : launch_bwd<DMODE, kBwdBf16DS4, p6::kWgradStages>(gd, gw, dy, wt, dres, dx, x, ws, rj, s,
                                                                                order);
 }
 
@@ -2125,17 +2007,14 @@ int launch_bwd_mode(int dtype, int ds, const Geom& gd, const p6::WGeom& gw, cons
 // otherwise as the separate pose6d_conv2d_dgrad + pose6d_conv2d_wgrad launches.
 // dx == NULL: weight gradient only.
 namespace {
-#ifndef POSE6D_BWD_F32_FUSE128
-#define POSE6D_BWD_F32_FUSE128 1   // build-time (A/B): 0 = the fp32 128x128 weight gradients as launches of their own
-#endif
 bool bwd_fused(int dtype, const Plan& pd, const p6::WgradPlan& pw, const pose6d_tuning_t* tn) {
   // the fused kernels carry the 64x64 weight-gradient bodies (conv_bwd_kernel) and the
   // bf16 128x128 one (conv_bwd8_kernel: its data gradient on 128x64 tiles of 8 waves)
   if (!pd.fast || pd.tile != 3 || !(pd.stages == 2 || pd.stages == 4) || !pw.fast) return false;
-  if (tune(tn, &pose6d_tuning_t::bwd_separate, 0) != 0) return false;
+  if (tuned(tn, &pose6d_tuning_t::bwd_separate, 0) != 0) return false;
   if (pw.bm == 128 && dtype == POSE6D_DT_BF16) return pw.stages == 2 || pw.stages == 3;
-  if (pw.bm == 128) return POSE6D_BWD_F32_FUSE128 && pw.stages == POSE6D_WGRAD_STAGES_F32;   // fp32 KxK, 128x128
-  return pw.bm == 64 && pw.stages == (dtype == POSE6D_DT_BF16 ? POSE6D_WGRAD_STAGES : POSE6D_WGRAD_STAGES_F32);
+  if (pw.bm == 128) return pw.stages == p6::kWgradStagesF32;   // fp32 KxK, 128x128
+  return pw.bm == 64 && pw.stages == (dtype == POSE6D_DT_BF16 ? p6::kWgradStages : p6::kWgradStagesF32);
 }
 
 // the data-gradient plan a fused launch runs: the bf16 8-wave launch (128x128 weight-
@@ -2231,15 +2110,11 @@ int conv_backward_impl(int32_t dtype, const void* x, const void* dy, const void*
   Geom gd = pd.g;
   set_bnr(gd, bnr);
   const ReduceJob& carried = rj ? *rj : none;
-  const int order = tune(tn, &pose6d_tuning_t::bwd_order, -1);
+  const int order = tuned(tn, &pose6d_tuning_t::bwd_order, -1);
   // one weight-gradient split of a 1x1 conv whose K is exactly Cin (layer4's 1x1 convs):
   // the slab [Cout][Cin] IS the OIHW dW, so the launch writes dW itself and no reduce
-  // follows (the reduce would only have copied it)
-#ifndef POSE6D_WGRAD_DIRECT
-#define POSE6D_WGRAD_DIRECT 1   // build-time (A/B): 0 = every plan through the slab reduce
-#endif
-  const bool direct = POSE6D_WGRAD_DIRECT && gw.splits == 1 && KH == 1 && KW == 1 && gw.Kpad == Cin &&
-                      Cin_real == Cin && !accumulate;
+  // follows (the reduce would only have copied it; profiles/r04_wgrad_direct_ab.txt)
+  const bool direct = gw.splits == 1 && KH == 1 && KW == 1 && gw.Kpad == Cin && Cin_real == Cin && !accumulate;
   float* slab = direct ? dw : workspace;
   if ((phases & 1) && pw.bm == 128 && dtype == POSE6D_DT_BF16) {
     switch (pd.mode) {

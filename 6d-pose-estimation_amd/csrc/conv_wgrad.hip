@@ -306,32 +306,34 @@ int launch_fast_f32_any(const Plan& p, const WGeom& g, const void* x, const void
   return p.stages == 3 ? launch_fast_f32<3, 64>(g, x, dy, ws, s, rj) : launch_fast_f32<2, 64>(g, x, dy, ws, s, rj);
 }
 
-int tuned(const pose6d_tuning_t* t, int32_t pose6d_tuning_t::*f, int dflt) {
-  return (t && t->*f >= 0) ? (int)(t->*f) : dflt;
-}
+using p6::tuned;
 
-// build-time (A/B sweeps): workgroups the bf16 / register-staged (fp32, stem) split
-// plans aim for, and the bf16 LDS ring depth
-#ifndef POSE6D_WGRAD_TARGET
-#define POSE6D_WGRAD_TARGET 256
-#endif
-#ifndef POSE6D_WGRAD_TARGET_KXK
-#define POSE6D_WGRAD_TARGET_KXK 256
-#endif
-#ifndef POSE6D_WGRAD_TARGET_BASE
-#define POSE6D_WGRAD_TARGET_BASE 1024
-#endif
-#ifndef POSE6D_WGRAD_TARGET_F32
-#define POSE6D_WGRAD_TARGET_F32 512
-#endif
-#ifndef POSE6D_WGRAD_TARGET_F32_FAST
-#define POSE6D_WGRAD_TARGET_F32_FAST 512
-#endif
+// ---- launch planning: the kernel, its LDS ring, the workgroup target by shape class, the splits ----
 
+// workgroups (tiles x splits) a plan aims for, by shape class:
+// bf16 LDS-DMA 64x64 tiles, 1x1 and KxK alike: about one per CU (profiles/r03w_wgrad_target_ab.txt,
+// profiles/r03y_wgrad_kxk_target_ab.txt)
+constexpr int kTargetBf16 = 256;
+// bf16 LDS-DMA 128x128 tiles: fewer slabs for the next launch to read back (profiles/r06_bf128_target.txt)
+constexpr int kTargetBf128 = 192;
+// the row-tap stems' 4 K-tiles: ~4 workgroups per CU (profiles/r05w_stem_wgrad_sweep.txt)
+constexpr int kTargetRowtap = 1024;
+// fp32 LDS-DMA tiles: ~2 workgroups per CU (profiles/r05ft_f32_wgrad_target_ab.txt)
+constexpr int kTargetF32Fast = 512;
+// register-staged kernel: fp32 convs / the bf16 stem (profiles/r03x_wgrad_base_target_ab.txt)
+constexpr int kTargetF32 = 512;
+constexpr int kTargetBase = 1024;
+// plans with at least this many tiles take ONE split (a tile's whole pixel range in one workgroup):
+// fp32 64x64 (layer4's 512 -> 2048 / 2048 -> 512 1x1 convs, profiles/r04_bwd_plan_sweep.txt) and
+// bf16 128x128 (layer4's 3x3 convs, profiles/r06_l4_onesplit.txt)
+constexpr int kF32OneSplitTiles = 256;
+constexpr int kBf128OneSplitTiles = 128;
+// fp32 LDS-DMA tile of the KxK convs wider than 64 channels (profiles/r04_f32_conv_sweep.txt)
+constexpr int kF32KxKTile = 128;
+// ring slots of the bf16 128x128 weight gradient (profiles/r06_wgrad128_ring3_rejected.txt)
+constexpr int kWgradStagesBf128 = 2;
 
-#ifndef POSE6D_WGRAD_F32_KXK_BT
-#define POSE6D_WGRAD_F32_KXK_BT 128
-#endif
+int clamp(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
 
 // bf16 weight gradients take the LDS-DMA kernel (64x64 tiles, 3-slot ring) unless a
 // pose6d_tuning_t (tests / tools only) asks for the register-staged kernel or another ring
@@ -341,134 +343,65 @@ int tuned(const pose6d_tuning_t* t, int32_t pose6d_tuning_t::*f, int dflt) {
 // workgroup waiting on its DMA: 56 -> 34 us graph-timed (profiles/r05w_stem_wgrad_sweep.txt).
 // The fp32 row-tap stem keeps the fp32 default (512 -> 128 splits of its 4 tiles: 147 us
 // against 156 at 256 splits and 160 register-staged, profiles/r05w32_f32_stem_wgrad.txt)
-#ifndef POSE6D_WGRAD_BF128
-#define POSE6D_WGRAD_BF128 1   // build-time (A/B): 0 = the bf16 weight gradients on 64x64 tiles only, 2 = 128x128 wherever eligible
-#endif
 // wide: the geometry prefers the bf16 128x128 / 8-wave tile (KxK filters and stride-2 1x1
 // convs: graph-timed alone 24-35 % faster than 64x64 on the 3x3 convs and the 28x28
-// 512 -> 1024 downsample, slower on most stride-1 1x1 convs; profiles/r06_wgrad128_sweep.txt)
+// 512 -> 1024 downsample, slower on most stride-1 1x1 convs; profiles/r06_wgrad128.txt)
 Plan plan(int dtype, int M, int Cout, int Kpad, int SC, const pose6d_tuning_t* tn = nullptr, bool rowtap = false,
           bool wide = false) {
   Plan p{};
-  // wgrad_base: 0 = default, 1 = register-staged; fp32 only: 2 = LDS-DMA 64x64 tiles,
-  // 3 = LDS-DMA 128x128 tiles (each where the channel counts allow it, else the default)
+  const bool f32 = dtype == POSE6D_DT_F32;
+  // 1. the kernel.  wgrad_base: 0 = default, 1 = register-staged; fp32 only: 2 = LDS-DMA
+  // 64x64 tiles, 3 = LDS-DMA 128x128 tiles (each where the channel counts allow it, else
+  // the default); bf16 only: 4 = the 128x128 / 8-wave LDS-DMA tile, 5 = the 64x64 tile
+  // wherever the default would take 128x128 (tools)
   const int wb = tuned(tn, &pose6d_tuning_t::wgrad_base, 0);
   const bool ok64 = SC % 64 == 0 && Cout % 64 == 0, ok128 = SC % 128 == 0 && Cout % 128 == 0;
   int f32_bt = 0;
-  if (dtype == POSE6D_DT_F32 && wb != 1) {
+  if (f32 && wb != 1) {
     // default: 64x64 tiles for 1x1 filters and for Cout = 64, 128x128 for wider KxK
     // convs (the 64x64 body lost to the register-staged 128x128 tile there: 28x28
     // 128->128 3x3 85 vs 131 us, profiles/r04_f32_conv_sweep.txt)
     if (wb == 2 && ok64) f32_bt = 64;
     else if (wb == 3 && ok128) f32_bt = 128;
     else if (ok64 && (Kpad == SC || Cout == 64)) f32_bt = 64;
-    else if (ok128) f32_bt = POSE6D_WGRAD_F32_KXK_BT;
+    else if (ok128) f32_bt = kF32KxKTile;
   }
-  // bf16: wgrad_base 4 = the 128x128 / 8-wave LDS-DMA tile (Cout and the padded K multiples
-  // of 128; a 128-wide K tile may span two filter taps of 64 channels)
-  // (wgrad_base 5: the 64x64 tile wherever the default would take 128x128; tools)
-  const bool bf128 = dtype == POSE6D_DT_BF16 &&
-                     (wb == 4 || (wb == 0 && (POSE6D_WGRAD_BF128 == 2 || (wide && POSE6D_WGRAD_BF128)))) && ok64 &&
-                     Cout % 128 == 0 && Kpad % 128 == 0 && !rowtap;
-  p.fast = dtype == POSE6D_DT_F32 ? f32_bt != 0 : ok64 && (wb == 0 || wb == 5 || bf128);
-  int target, min_rows, step;
-  int64_t max_bytes;
-  if (p.fast && dtype == POSE6D_DT_F32) {
-    // fp32 LDS-DMA body: 32 KiB stages, 2 slots (two workgroups per CU), ~2
-    // workgroups per CU of splits
-    p.bm = f32_bt;
-    p.bn = f32_bt;
-    p.stages = tuned(tn, &pose6d_tuning_t::wgrad_stages, POSE6D_WGRAD_STAGES_F32);
-    if (p.stages < 2) p.stages = 2;
-    if (p.stages > 3) p.stages = 3;
-    target = POSE6D_WGRAD_TARGET_F32_FAST;
-    min_rows = 256;
-    step = f32_bt == 128 ? f32_ms<128>() : f32_ms<64>();
-    max_bytes = 64ll << 20;
-  } else if (p.fast) {
-    p.bm = bf128 ? 128 : 64;
-    p.bn = bf128 ? 128 : 64;
-#ifndef POSE6D_WGRAD_STAGES_BF128
-#define POSE6D_WGRAD_STAGES_BF128 2   // build-time (A/B): ring slots of the bf16 128x128 weight gradient
-#endif
-    p.stages = tuned(tn, &pose6d_tuning_t::wgrad_stages, bf128 ? POSE6D_WGRAD_STAGES_BF128 : POSE6D_WGRAD_STAGES);
-    if (p.stages < 2) p.stages = 2;
-    if (p.stages > (bf128 ? 3 : 4)) p.stages = bf128 ? 3 : 4;
-    // ~256 workgroups (one per CU): with the fused launch dispatching its longest
-    // workgroups first, long weight-gradient splits no longer form its tail, and
-    // fewer splits write and reduce fewer fp32 slabs.  End-to-end A/B on one box
-    // (profiles/r03w_wgrad_target_ab.txt): 256 / 384 / 448 / 512 / 640 / 896 / 1280 ->
-    // 4.64 / 4.70 / 4.65 / 4.65 / 4.71 / 4.81 / 4.89 ms per step (640 was the best
-    // target while the data gradient went first: 5.14 ms then, 384 -> 5.24)
-    target = Kpad == SC ? POSE6D_WGRAD_TARGET : POSE6D_WGRAD_TARGET_KXK;   // 1x1 / larger filters
-    if (rowtap) {
-      target = 1024;
-      p.stages = tuned(tn, &pose6d_tuning_t::wgrad_stages, 2);
-      if (p.stages < 2) p.stages = 2;
-      if (p.stages > 4) p.stages = 4;
-    }
-    min_rows = 256;
-    step = 64;
-    max_bytes = 48ll << 20;
-  } else {
+  // bf16 128x128: Cout and the padded K multiples of 128 (a 128-wide K tile may span two
+  // filter taps of 64 channels)
+  const bool bf128 = !f32 && (wb == 4 || (wb == 0 && wide)) && ok64 && Cout % 128 == 0 && Kpad % 128 == 0 && !rowtap;
+  p.fast = f32 ? f32_bt != 0 : ok64 && (wb == 0 || wb == 5 || bf128);
+  if (!p.fast) {
     p.bm = Cout >= 128 ? 128 : 64;
     p.bn = Kpad >= 128 ? 128 : 64;
-    // fp32 (all convs) / the bf16 stem; sweeps in profiles/r03x_wgrad_base_target_ab.txt:
-    // fp32 step 256 / 384 / 512 / 1024 / 2048 -> 13.73 / 13.63 / 13.04 / 13.36 / 13.38 ms,
-    // the bf16 step with 512 for its stem 4.665 vs 4.636 ms at 1024
-    target = dtype == POSE6D_DT_F32 ? POSE6D_WGRAD_TARGET_F32 : POSE6D_WGRAD_TARGET_BASE;
-    min_rows = 256;
-    step = MT;
-    max_bytes = 64ll << 20;   // stem: 16 -> 64 MiB of slabs, 90 -> 65 us
+  } else {
+    p.bm = p.bn = f32 ? f32_bt : bf128 ? 128 : 64;
   }
   const int tiles = p6::ceil_div(Cout, p.bm) * p6::ceil_div(Kpad, p.bn);
-  // fp32 128x128 plans with many tiles (layer4's 3x3 convs: 144 tiles over 1568 pixels)
-  // take twice the workgroups: 8 splits of 196 pixels, 207 -> 184 us on 7x7 512->512;
-  // the few-tile KxK shapes keep the default target (profiles/r04_fp32_kxk_splits.txt)
-#ifndef POSE6D_WGRAD_F32_MANY_TILES
-#define POSE6D_WGRAD_F32_MANY_TILES 100000   // build-time (A/B): tiles from which the target doubles (round 6: off -- neutral to -0.2 %
-                                           // the doubled slabs are read back by the next launch; profiles/r06_f32_split.txt)
-#endif
-  if (p.fast && dtype == POSE6D_DT_F32 && p.bm == 128 && tiles >= POSE6D_WGRAD_F32_MANY_TILES) target *= 2;
-  // fp32 64x64 plans with >= 256 tiles (layer4's 512 -> 2048 / 2048 -> 512 1x1 convs): one
-  // split -- a tile's 1568 pixels in one workgroup, 93 -> 78 us on 7x7 512->2048
-  // (profiles/r04_bwd_plan_sweep.txt)
-#ifndef POSE6D_WGRAD_F32_ONE_SPLIT_TILES
-#define POSE6D_WGRAD_F32_ONE_SPLIT_TILES 256   // build-time (A/B)
-#endif
-  if (p.fast && dtype == POSE6D_DT_F32 && p.bm == 64 && tiles >= POSE6D_WGRAD_F32_ONE_SPLIT_TILES) target = tiles;
-#ifndef POSE6D_WGRAD_BF128_ONE_SPLIT_TILES
-#define POSE6D_WGRAD_BF128_ONE_SPLIT_TILES 128   // bf16 128x128 plans with >= this many tiles (layer4 3x3): one split
-                                                 // (no slab round trip in the next launch: 4.532 -> 4.515 ms, profiles/r06_l4_onesplit.txt)
-#endif
-#ifndef POSE6D_WGRAD_F32_128_ONE_SPLIT_TILES
-#define POSE6D_WGRAD_F32_128_ONE_SPLIT_TILES 0   // build-time (A/B): fp32 128x128 plans with >= this many tiles: one split
-#endif
-  if (POSE6D_WGRAD_F32_128_ONE_SPLIT_TILES > 0 && p.fast && dtype == POSE6D_DT_F32 && p.bm == 128 &&
-      tiles >= POSE6D_WGRAD_F32_128_ONE_SPLIT_TILES)
-    target = tiles;
-#ifndef POSE6D_WGRAD_F32_128_TARGET
-#define POSE6D_WGRAD_F32_128_TARGET 0   // build-time (A/B): workgroup target of the fp32 128x128 plans (0 = default)
-#endif
-  if (POSE6D_WGRAD_F32_128_TARGET > 0 && p.fast && dtype == POSE6D_DT_F32 && p.bm == 128)
-    target = POSE6D_WGRAD_F32_128_TARGET;
-#ifndef POSE6D_WGRAD_BF128_TARGET
-#define POSE6D_WGRAD_BF128_TARGET 192   // workgroup target of the bf16 128x128 plans (0 = the KxK target, 256): fewer
-                                        // slabs for the next launch to read back (profiles/r06_bf128_target.txt)
-#endif
-  if (POSE6D_WGRAD_BF128_TARGET > 0 && p.fast && dtype == POSE6D_DT_BF16 && p.bm == 128)
-    target = POSE6D_WGRAD_BF128_TARGET;
-  if (POSE6D_WGRAD_BF128_ONE_SPLIT_TILES > 0 && p.fast && dtype == POSE6D_DT_BF16 && p.bm == 128 &&
-      tiles >= POSE6D_WGRAD_BF128_ONE_SPLIT_TILES)
-    target = tiles;
-#ifndef POSE6D_WGRAD_NARROW1X1_TARGET
-#define POSE6D_WGRAD_NARROW1X1_TARGET 0   // build-time (A/B): target of the bf16 1x1 256 -> 64 weight gradients (layer1's
-                                          // residual-junction convs; 0 = the 1x1 target)
-#endif
-  if (POSE6D_WGRAD_NARROW1X1_TARGET > 0 && p.fast && dtype == POSE6D_DT_BF16 && Kpad == SC && Cout == 64 &&
-      Kpad >= 4 * Cout)
-    target = POSE6D_WGRAD_NARROW1X1_TARGET;
-  // aim for ~`target` workgroups, each reducing >= min_rows pixels, slabs capped in bytes
+
+  // 2. the LDS ring (the register-staged kernel has none) and the pixel step of a split
+  int step = MT;
+  if (p.fast && f32) {
+    // 32 KiB stages, 2 slots: two workgroups per CU
+    p.stages = clamp(tuned(tn, &pose6d_tuning_t::wgrad_stages, p6::kWgradStagesF32), 2, 3);
+    step = f32_bt == 128 ? f32_ms<128>() : f32_ms<64>();
+  } else if (p.fast) {
+    const int dflt = bf128 ? kWgradStagesBf128 : rowtap ? 2 : p6::kWgradStages;
+    p.stages = clamp(tuned(tn, &pose6d_tuning_t::wgrad_stages, dflt), 2, bf128 ? 3 : 4);
+    step = 64;
+  }
+
+  // 3. the workgroup target, one rule per shape class
+  int target;
+  if (!p.fast) target = f32 ? kTargetF32 : kTargetBase;
+  else if (f32) target = p.bm == 64 && tiles >= kF32OneSplitTiles ? tiles : kTargetF32Fast;
+  else if (rowtap) target = kTargetRowtap;
+  else if (bf128) target = tiles >= kBf128OneSplitTiles ? tiles : kTargetBf128;
+  else target = kTargetBf16;
+
+  // 4. the splits: ~`target` workgroups, each reducing >= min_rows pixels, slabs capped in
+  // bytes (the register-staged stem: 16 -> 64 MiB of slabs, 90 -> 65 us)
+  const int min_rows = 256;
+  const int64_t max_bytes = (p.fast && !f32) ? 48ll << 20 : 64ll << 20;
   int splits = p6::ceil_div(target, tiles);
   const int max_splits = p6::ceil_div(M, min_rows);
   if (splits > max_splits) splits = max_splits;

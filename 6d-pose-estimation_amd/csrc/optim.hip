@@ -286,13 +286,7 @@ __global__ __launch_bounds__(kThreads) void adamw_packed_kernel(float* __restric
   }
   if (taps == 1 && d.wt == nullptr) return;
   __syncthreads();
-#ifndef POSE6D_ADAMW_NOWP   // (timing-only builds: tools/adamw_bench.py)
-#define POSE6D_ADAMW_NOWP 0
-#endif
-#ifndef POSE6D_ADAMW_NOWT
-#define POSE6D_ADAMW_NOWT 0
-#endif
-  if (taps > 1 && !POSE6D_ADAMW_NOWP) {
+  if (taps > 1) {
     // wp[o][ptap*Ip + c0 + ci], ci < cw: column ci*taps + tap of the tile, at packed tap
     // ptap = kh*KWp + kw + KWp - KW (KWp = KW but for the row-tap stems)
     const int kwp = d.KWp > 0 ? d.KWp : d.KW;
@@ -311,7 +305,7 @@ __global__ __launch_bounds__(kThreads) void adamw_packed_kernel(float* __restric
       }
     }
   }
-  if (d.wt == nullptr || POSE6D_ADAMW_NOWT) return;
+  if (d.wt == nullptr) return;
   // wt[r][o] for the tile's columns r: eight filters per store
   T* wt = reinterpret_cast<T*>(d.wt) + (int64_t)r0 * d.O + o0;
   if ((rows & 7) == 0 && (d.O & 7) == 0) {

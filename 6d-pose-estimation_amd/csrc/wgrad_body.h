@@ -5,18 +5,15 @@
 #include "common.h"
 #include "lds_dma.h"
 
-// LDS ring depth of the bf16 weight-gradient kernel (standalone and inside the fused
-// backward launch); build-time only, for A/B timing
-#ifndef POSE6D_WGRAD_STAGES
-#define POSE6D_WGRAD_STAGES 3
-#endif
-// LDS ring depth of the fp32 weight-gradient body (32 KiB stages): two slots keep two
-// workgroups per CU resident
-#ifndef POSE6D_WGRAD_STAGES_F32
-#define POSE6D_WGRAD_STAGES_F32 2
-#endif
-
 namespace p6 {
+
+// LDS ring depth of the bf16 64x64 weight-gradient kernel, standalone and inside the
+// fused backward launch: a workgroup's DMA rate does not rise past 3 slots
+// (profiles/r04_ldsdma_rates.txt)
+constexpr int kWgradStages = 3;
+// LDS ring depth of the fp32 weight-gradient body (32 KiB stages): two slots keep two
+// workgroups per CU resident; 3 slots measured slower (profiles/r04_f32_wgrad_ab.txt)
+constexpr int kWgradStagesF32 = 2;
 
 struct WGeom {
   int M, Cout, K, Kpad;
@@ -588,6 +585,9 @@ __device__ __forceinline__ void conv_wgrad_lds_body_f32(char* smem, int bid, con
 // LDS in group order (deterministic).  G is picked so that small gradients with
 // hundreds of splits still spread their reads over many lanes.  `blk` = this
 // workgroup's index among the reduce's workgroups; `red` = 256 float4 of LDS.
+// The body contains exactly ONE workgroup barrier, reached by all 256 threads whatever
+// `ok` is.  conv_bwd8_kernel (512 threads) runs it on its lower four waves and matches it
+// with one bare barrier on its upper four: a second barrier here needs a second one there.
 template <int G>
 __device__ __forceinline__ void wgrad_reduce_body(float4* red, int blk, const float* __restrict__ ws,
                                                   float* __restrict__ dw, int Cout, int Kpad, int SC, int Cin, int KH,

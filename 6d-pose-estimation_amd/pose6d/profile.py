@@ -47,8 +47,8 @@ def conv_launches(eng, fused=True):
         if bv:
             # the step's fused data + weight gradient launch (conv2d_backward phase 1;
             # the slab reduce is its own kernel and row in rocprof)
-            # conv_bwd_kernel<DMODE, DS, WS[, float]>: WS = POSE6D_WGRAD_STAGES (3, bf16) or
-            # POSE6D_WGRAD_STAGES_F32 (2, fp32; csrc/wgrad_body.h)
+            # conv_bwd_kernel<DMODE, DS, WS[, float]>: WS = kWgradStages (3, bf16) or
+            # kWgradStagesF32 (2, fp32; csrc/wgrad_body.h)
             if eng.dtype == torch.float32:
                 sym = f"conv_bwd_kernel<{(bv >> 4) & 15}, {bv & 15}, 2, float>"
             else:

@@ -291,8 +291,8 @@ def test_trunk_finalize_act_one_launch_is_bit_identical(dtype):
     workgroups waiting on the finalize workgroups' ready flags) against the two launches
     it replaces (pose6d_bn_finalize + pose6d_bn_act_fwd_mask): every activation, ReLU
     mask, batch statistic, running statistic and the features bit for bit, over three
-    training forwards (epochs advance), at batch 8 (rows <= 512: the one-wave fold) and
-    batch 32 (layer1/2: rows > 512, the workgroup fold)."""
+    training forwards (epochs advance), at batch 8 (rows <= 512) and batch 32 (layer1/2:
+    rows > 512); every row count takes the one-workgroup-per-channel fold."""
     import copy
     from models.pose_net_rgbd_geometric import PoseNetRGBDGeometric
     from pose6d.trunk import TrunkEngine, _ActOp, _ConvOp
@@ -327,17 +327,18 @@ def test_trunk_finalize_act_one_launch_is_bit_identical(dtype):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("rows_case", ["wave_fold", "block_fold"])
+@pytest.mark.parametrize("rows_case", ["rows196", "rows784"])
 def test_bn_finalize_act_fallback_is_bit_identical(rows_case):
     """The apply workgroups' own fold (taken when the finalize's ready flags do not arrive
     in time; forced here with a negative epoch) gives the finalize's scale / shift bits:
-    the fused launch's outputs equal the two-launch path's."""
+    the fused launch's outputs equal the two-launch path's, at 196 and at 784 partial rows
+    per channel (both the workgroup fold: one row per lane at most, and several)."""
     import ctypes
     from pose6d._lib import DT_BF16, call, stream
     from pose6d.trunk import _BnStats
     torch.manual_seed(1)
     dev = "cuda"
-    M = 6272 if rows_case == "wave_fold" else 25088   # rows 196 (<= 512) / 784
+    M = 6272 if rows_case == "rows196" else 25088   # rows 196 / 784
     C = 256
     rows = (M + 31) // 32
     y = (torch.randn(M, C, device=dev) * 2 + 0.3).bfloat16()

@@ -1,0 +1,90 @@
+"""The launch plan of every trunk convolution, pinned against a committed table.
+
+Host-only plan queries (no device): for every distinct conv geometry of the four models'
+trunks (the ResNet50 trunk they share and the z-CNN of the RGB-Geometric model) at a
+224x224 input, at batch 1, 2, 8 and 32, fp32 and bf16, the forward / data-gradient
+variant, the forward split-K workspace, the patch plan, the weight-gradient variant and
+workspace (which exposes the split count) and the fused-backward variant must equal
+tests/golden/conv_plans.json.  A change to a planning rule has to update that table on
+purpose: run this file as a script against the library whose plans are the new truth,
+
+    POSE6D_LIB=/path/to/libpose6d.so python tests/test_conv_plans.py
+
+which rewrites the table.  Batches 1 and 2 are there because the small-grid split-K rule
+and the one-split weight-gradient rules fire only on them.
+"""
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIXTURE = os.path.join(REPO, "tests", "golden", "conv_plans.json")
+BATCHES = (1, 2, 8, 32)
+QUERIES = ("fwd_variant", "dgrad_variant", "fwd_splitk_workspace", "patch_plan", "wgrad_variant", "wgrad_workspace",
+           "bwd_variant")
+
+
+def trunk_geometries():
+    """{name: (H, W, cin_pad, cout, k, stride, pad, Ho, Wo)}: the distinct conv geometries of
+    the trunks, named after the first conv that has each (padded channel counts, as
+    pose6d/profile.py passes them)."""
+    import warnings
+
+    from models.pose_net_rgb_geometric import PoseNetRGBGeometric
+    from pose6d.trunk import TrunkEngine
+
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        m = PoseNetRGBGeometric(pretrained=False)
+    geoms, seen = {}, set()
+    for seq, kind in ((m.rgb_backbone, "resnet50"), (m.z_backbone, "zcnn")):
+        for op in TrunkEngine(seq, 3, kind).convs:
+            g = (op.H, op.W, op.cin_pad, op.cout, op.k, op.stride, op.pad, op.Ho, op.Wo)
+            if g not in seen:
+                seen.add(g)
+                geoms[op.name] = g
+    return geoms
+
+
+def plan_table():
+    """{"<conv> b<batch> <dtype>": {query: value}} from the loaded library."""
+    from pose6d._lib import DT_BF16, DT_F32, query
+
+    table = {}
+    for name, (H, W, cin, cout, k, s, p, Ho, Wo) in trunk_geometries().items():
+        for B in BATCHES:
+            for dname, dt in (("f32", DT_F32), ("bf16", DT_BF16)):
+                conv = (B, H, W, cin, cout, k, k, s, p, Ho, Wo)
+                table[f"{name} b{B} {dname}"] = dict(zip(QUERIES, (
+                    query("conv_variant", dt, 0, *conv),
+                    query("conv_variant", dt, 1, *conv),
+                    query("conv_splitk_workspace", dt, 0, *conv),
+                    query("conv_patch_plan", dt, *conv),
+                    query("wgrad_variant", dt, B * Ho * Wo, cout, k * k * cin, cin),
+                    query("conv2d_wgrad_workspace", dt, B, Ho, Wo, cin, cout, k, k),
+                    query("bwd_variant", dt, *conv))))
+    return table
+
+
+def generate(path=FIXTURE):
+    with open(path, "w") as f:
+        json.dump(plan_table(), f, indent=0, sort_keys=True)
+        f.write("\n")
+
+
+def test_trunk_conv_plans_match_the_pinned_table():
+    with open(FIXTURE) as f:
+        want = json.load(f)
+    got = plan_table()
+    assert sorted(got) == sorted(want), "the set of (conv, batch, dtype) entries changed"
+    assert len(got) == len(trunk_geometries()) * len(BATCHES) * 2
+    bad = [f"{key}: {q} = {got[key][q]} (0x{got[key][q]:x}), pinned {want[key][q]} (0x{want[key][q]:x})"
+           for key in sorted(want) for q in QUERIES if got[key][q] != want[key][q]]
+    assert not bad, "launch plans differ from tests/golden/conv_plans.json:\n" + "\n".join(bad)
+
+
+if __name__ == "__main__":
+    for _p in (REPO, os.path.join(REPO, "6d-pose-estimation_amd")):
+        if _p not in sys.path:
+            sys.path.insert(0, _p)
+    generate(sys.argv[1] if len(sys.argv) > 1 else FIXTURE)

@@ -1,7 +1,7 @@
-"""A/B of the ADD/ADD-S points kernel variants (POSE6D_ADD_VARIANT, read once per
-process): times pose6d_add_eval on BASELINE configs[3] (bs256 x 2000 pts x 13 objects)
-and saves min / argmin so the variants can be compared bit for bit.
-usage: POSE6D_ADD_VARIANT=k python tools/add_ab.py OUT.npz"""
+"""A/B of two builds of the ADD/ADD-S points kernel: times pose6d_add_eval on BASELINE
+configs[3] (bs256 x 2000 pts x 13 objects) and saves min / argmin so the builds can be
+compared bit for bit.
+usage: [POSE6D_LIB=/other/checkout/libpose6d.so] python tools/add_ab.py OUT.npz"""
 import os
 import sys
 
@@ -39,7 +39,7 @@ def main():
         ts.append(e0.elapsed_time(e1) / 10)
     ms = sorted(ts)[2]
     pairs = float(sum(pts[int(i)].shape[0] ** 2 for i in ids))
-    print(f"variant {os.environ.get('POSE6D_ADD_VARIANT', '0')}: {ms:.4f} ms/batch, {pairs / ms / 1e9:.3f} T pairs/s, "
+    print(f"{os.environ.get('POSE6D_LIB', 'default build')}: {ms:.4f} ms/batch, {pairs / ms / 1e9:.3f} T pairs/s, "
           f"{pairs * 8 / ms / 1e9 / 157.3:.3f} of 157.3 TF", flush=True)
     np.savez(sys.argv[1], min=out["min"].cpu().numpy(), argmin=out["argmin"].cpu().numpy(),
              adds=out["adds"].cpu().numpy())
