@@ -644,6 +644,63 @@ __global__ __launch_bounds__(kThreads) void channel_sum_kernel(const T* __restri
   }
 }
 
+// The same sum for long tensors (the z-CNN's conv biases: 32 channels over 400 K pixels at
+// batch 32, where one block per 64 channels runs for milliseconds), in two deterministic
+// passes.  Pass 1: row block blockIdx.x sums its rows -- a thread owns one 16-byte channel
+// chunk (cpr = C / E chunks per row, a power of two <= kThreads) of every (kThreads / cpr)-th
+// row, then the row lanes are added through LDS in order -> part[block][C].  Pass 2: one
+// workgroup per 64 channels adds the blocks' partials in a fixed order.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void channel_sum_part_kernel(const T* __restrict__ x, int64_t M, int C,
+                                                                    int rows_per_block,
+                                                                    float* __restrict__ part) {
+  constexpr int E = V<T>::E;
+  __shared__ float red[kThreads * E];
+  const int cpr = C / E, rpt = kThreads / cpr;
+  const int ch = (threadIdx.x % cpr) * E, r0 = threadIdx.x / cpr;
+  const int64_t lo = (int64_t)blockIdx.x * rows_per_block;
+  const int64_t hi = lo + rows_per_block < M ? lo + rows_per_block : M;
+  float s[E];
+#pragma unroll
+  for (int e = 0; e < E; ++e) s[e] = 0.f;
+#pragma unroll 4
+  for (int64_t m = lo + r0; m < hi; m += rpt) {
+    float v[E];
+    load_vec(x + m * C + ch, v);
+#pragma unroll
+    for (int e = 0; e < E; ++e) s[e] += v[e];
+  }
+#pragma unroll
+  for (int e = 0; e < E; ++e) red[r0 * C + ch + e] = s[e];
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += kThreads) {
+    float a = 0.f;
+    for (int r = 0; r < rpt; ++r) a += red[r * C + c];
+    part[(int64_t)blockIdx.x * C + c] = a;
+  }
+}
+
+// (64 channels per workgroup, four lanes per channel each adding every fourth partial --
+// independent loads, unrolled -- then the four in order: one thread per channel walking up
+// to 512 partials one load at a time took ~100 us)
+__global__ __launch_bounds__(kThreads) void channel_sum_fin_kernel(const float* __restrict__ part, int blocks, int C,
+                                                                   float* __restrict__ out, int accumulate) {
+  __shared__ float red[4][64];
+  const int cl = threadIdx.x & 63, pr = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + cl;
+  float a = 0.f;
+  if (c < C) {
+#pragma unroll 8
+    for (int b = pr; b < blocks; b += 4) a += part[(int64_t)b * C + c];
+  }
+  red[pr][cl] = a;
+  __syncthreads();
+  if (pr == 0 && c < C) {
+    a = red[0][cl] + red[1][cl] + red[2][cl] + red[3][cl];
+    out[c] = accumulate ? out[c] + a : a;
+  }
+}
+
 inline unsigned grid_for(int64_t chunks) {
   int64_t b = (chunks + kThreads - 1) / kThreads;
   // one chunk per thread for every ResNet50 activation at batch 32 (<= 12544 blocks): a
@@ -926,6 +983,37 @@ extern "C" int pose6d_channel_sum(int32_t dtype, const void* x, int64_t M, int32
     channel_sum_kernel<bf16><<<p6::ceil_div(C, 64), kThreads, 0, s>>>((const bf16*)x, M, C, out, accumulate);
   else
     channel_sum_kernel<float><<<p6::ceil_div(C, 64), kThreads, 0, s>>>((const float*)x, M, C, out, accumulate);
+  P6_LAUNCH_CHECK();
+  return POSE6D_OK;
+}
+
+// pose6d_channel_sum in two passes over `workspace` (any size: it bounds the number of row
+// blocks; fewer than two, or a channel count the chunked layout does not fit, falls back to
+// the one-launch kernel).  Deterministic: fixed summation order for a given (M, C, size).
+extern "C" int pose6d_channel_sum_ws(int32_t dtype, const void* x, int64_t M, int32_t C, float* out,
+                                     int32_t accumulate, float* workspace, int64_t workspace_floats, void* stream) {
+  P6_CHECK_ARG(dtype == POSE6D_DT_BF16 || dtype == POSE6D_DT_F32, "pose6d_channel_sum_ws: bad dtype");
+  P6_CHECK_ARG(M >= 0 && C > 0 && workspace_floats >= 0, "pose6d_channel_sum_ws: bad M / C / workspace size");
+  const int E = dtype == POSE6D_DT_BF16 ? V<bf16>::E : V<float>::E;
+  const int cpr = C / E;
+  const bool fits = C % E == 0 && cpr <= kThreads && (cpr & (cpr - 1)) == 0;
+  int64_t blocks = 0;
+  if (fits && workspace) {
+    const int rpt = kThreads / cpr;
+    blocks = (M + 8 * rpt - 1) / (8 * rpt);   // at least eight trips per block
+    if (blocks > 512) blocks = 512;
+    if (blocks > workspace_floats / C) blocks = workspace_floats / C;
+  }
+  if (blocks < 2) return pose6d_channel_sum(dtype, x, M, C, out, accumulate, stream);
+  const int rpb = p6::ceil_div(M, blocks);
+  blocks = p6::ceil_div(M, rpb);
+  hipStream_t s = p6::stream_of(stream);
+  if (dtype == POSE6D_DT_BF16)
+    channel_sum_part_kernel<bf16><<<(unsigned)blocks, kThreads, 0, s>>>((const bf16*)x, M, C, rpb, workspace);
+  else
+    channel_sum_part_kernel<float><<<(unsigned)blocks, kThreads, 0, s>>>((const float*)x, M, C, rpb, workspace);
+  P6_LAUNCH_CHECK();
+  channel_sum_fin_kernel<<<p6::ceil_div(C, 64), kThreads, 0, s>>>(workspace, (int)blocks, C, out, accumulate);
   P6_LAUNCH_CHECK();
   return POSE6D_OK;
 }

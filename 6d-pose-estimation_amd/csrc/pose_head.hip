@@ -276,6 +276,45 @@ __global__ __launch_bounds__(kThreads) void quat_head_loss_kernel(
   block_loss(sr, st, B, wr, wt, loss);
 }
 
+// PoseNetRGBGeometric's head + loss: the sibling whose translation is a DIFFERENTIABLE
+// pinhole of the predicted depth.  Per sample rot = raw / (||raw|| + 1e-8) (rownorm mode 1,
+// pose_net_rgb_geometric.py:75), trans = pinhole_z_fwd_kernel's arithmetic (no clamps,
+// :93-109), the PoseLoss terms, d loss / d rot for dloss = 1 taken back through the
+// normalise into draw, and dtrans = sign(trans - gt) * wt / (3 B) folded through the
+// pinhole into dz (pinhole_z_bwd_kernel's formula); the loss reduced in pose_loss_fwd's
+// order (rot / trans / loss bit-identical to the separate calls).
+__global__ __launch_bounds__(kThreads) void zgeo_head_loss_kernel(
+    const float* __restrict__ raw, const float* __restrict__ z, const float* __restrict__ bbox,
+    const float* __restrict__ K, int Kb, const float* __restrict__ gr, const float* __restrict__ gt, int64_t B,
+    float wr, float wt, int mode, float* __restrict__ rot, float* __restrict__ trans, float* __restrict__ loss,
+    float* __restrict__ draw, float* __restrict__ dz) {
+  float sr = 0.f, st = 0.f;
+  const float grot_scale = wr / (float)B, c = wt / (float)(3 * B);
+  for (int64_t b = threadIdx.x; b < B; b += kThreads) {
+    const float* xr = raw + 4 * b;
+    const float n = l2(xr, 4);
+    const float d = n + kGeoEps;
+    float q[4];
+    for (int i = 0; i < 4; ++i) { q[i] = xr[i] / d; rot[4 * b + i] = q[i]; }
+    float fx, fy, cx, cy;
+    load_K(K, Kb, b, fx, fy, cx, cy);
+    const float zz = z[b];
+    const float du = bbox[2 * b] - cx, dv = bbox[2 * b + 1] - cy;
+    const float t[3] = {du * zz / fx, dv * zz / fy, zz};
+    float drot[4], dt[3];
+    sr += rot_term(q, gr + 4 * b, mode, drot, grot_scale);
+    for (int i = 0; i < 3; ++i) {
+      trans[3 * b + i] = t[i];
+      const float e = t[i] - gt[3 * b + i];
+      st += fabsf(e);
+      dt[i] = e > 0.f ? c : (e < 0.f ? -c : 0.f);
+    }
+    dz[b] = dt[0] * du / fx + dt[1] * dv / fy + dt[2];
+    rownorm_bwd_row(xr, drot, n, 4, 1, draw + 4 * b);
+  }
+  block_loss(sr, st, B, wr, wt, loss);
+}
+
 inline unsigned nblk(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
 }  // namespace
@@ -371,6 +410,19 @@ extern "C" int pose6d_quat_head_loss(const float* raw, const float* trans, const
   quat_head_loss_kernel<<<1, kThreads, 0, p6::stream_of(stream)>>>(raw, trans, gt_rot, gt_trans, B, rot_weight,
                                                                    trans_weight, rot_mode, norm_mode, rot, loss,
                                                                    grad_raw, grad_trans);
+  P6_LAUNCH_CHECK();
+  return POSE6D_OK;
+}
+
+extern "C" int pose6d_zgeo_head_loss(const float* raw, const float* z, const float* bbox_center, const float* K,
+                                     int32_t K_batched, const float* gt_rot, const float* gt_trans, int64_t B,
+                                     float rot_weight, float trans_weight, int32_t rot_mode, float* rot, float* trans,
+                                     float* loss, float* grad_raw, float* grad_z, void* stream) {
+  P6_CHECK_ARG(B > 0, "pose6d_zgeo_head_loss: empty batch (the reference's mean would be NaN)");
+  P6_CHECK_ARG(rot_mode == 0 || rot_mode == 1, "pose6d_zgeo_head_loss: bad rot_mode %d", rot_mode);
+  zgeo_head_loss_kernel<<<1, kThreads, 0, p6::stream_of(stream)>>>(raw, z, bbox_center, K, K_batched, gt_rot, gt_trans,
+                                                                   B, rot_weight, trans_weight, rot_mode, rot, trans,
+                                                                   loss, grad_raw, grad_z);
   P6_LAUNCH_CHECK();
   return POSE6D_OK;
 }

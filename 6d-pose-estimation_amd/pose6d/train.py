@@ -3,7 +3,8 @@
 i.e. the per-batch body of the reference's train() loop
 (scripts/training/train_rgbd_geometric.py:97-115), without autograd or host syncs.
 RGBTrainer (at the end) is the same step for PoseNetRGB's two heads
-(scripts/training/train_rgb.py:95-141).
+(scripts/training/train_rgb.py:95-141), RGBGeometricTrainer for PoseNetRGBGeometric's two
+trunks (scripts/training/train_rgb_geometric.py:97-110).
 
 MI355X design:
   * one flat fp32 arena for parameters / gradients / AdamW moments (the module's
@@ -98,10 +99,11 @@ class RGBDGeometricTrainer:
         dev = next(model.parameters()).device
         self.dev = dev
         model.train()
-        self.trunk = TrunkEngine(model.backbone, 3)
-        self.trunk.set_dtype(dtype)
-        self.trunk.prepare(batch, 224, 224, dtype, dev)
-        order = self._build_heads(model) + self.trunk.params_in_grad_order()
+        self.trunks = self._build_trunks(model)
+        for t in self.trunks:
+            t.set_dtype(dtype)
+            t.prepare(batch, 224, 224, dtype, dev)
+        order = self._build_heads(model) + [p for t in self.trunks for p in t.params_in_grad_order()]
         assert len(order) == len(list(model.parameters())) and {id(p) for p in order} == \
             {id(p) for p in model.parameters()}
         self.arena = FlatArena(order, dev)
@@ -146,9 +148,15 @@ class RGBDGeometricTrainer:
         self.graphs = None
         self._buckets(bucket_mb, tail_mb)
 
+    def _build_trunks(self, model):
+        """The trunk engines, in the order their backwards run (the arena's order after
+        the heads); self.trunk is the ResNet50."""
+        self.trunk = TrunkEngine(model.backbone, 3)
+        return [self.trunk]
+
     def _build_heads(self, model):
         """The head engines; returns their parameters in gradient-completion order (the
-        arena's prefix, ahead of the trunk's)."""
+        arena's prefix, ahead of the trunks')."""
         self.head = HeadEngine(model.rot_head)
         return self.head.params_in_grad_order()
 
@@ -156,7 +164,7 @@ class RGBDGeometricTrainer:
     def _build_jobs(self):
         """The work table of pose6d_adamw_step_packed (plain ranges and 64 x 64 conv
         tiles over the arena), built once: the arena and the packed buffers never move."""
-        rec = self.trunk._desc_host
+        rec = self._pack_descs()[0]
         args = (rec.ctypes.data, len(rec), self.arena.flat.data_ptr(), self.arena.numel)
         n = query("adamw_packed_jobs", *args, None, 0)
         if n <= 0:
@@ -167,20 +175,26 @@ class RGBDGeometricTrainer:
         self._jobs = torch.from_numpy(jobs).to(self.dev)
         self.n_jobs = n
 
+    def _pack_descs(self):
+        """(host, device) conv descriptor table that pose6d_adamw_packed_jobs /
+        pose6d_adamw_step_packed read: the trunk's own pack table."""
+        return self.trunk._desc_host, self.trunk._desc_dev
+
     def _weights_key(self):
         # writes through the arena (restore) bump flat's counter; in-place writes to a
         # Parameter (load_state_dict, `with torch.no_grad(): p.copy_(w)`) bump that
         # Parameter's own.  `p.data.copy_(w)` bumps neither (a `.data` alias carries a
         # fresh version counter): sync_weights() is the documented call after it
-        return (self.arena.flat._version,) + tuple(op.conv.weight._version for op in self.trunk.convs)
+        return (self.arena.flat._version,) + tuple(op.conv.weight._version for t in self.trunks for op in t.convs)
 
     def sync_weights(self):
-        """Re-pack the conv weights from the fp32 masters (one launch).  step() calls
+        """Re-pack the conv weights from the fp32 masters (one launch per trunk).  step() calls
         it itself when a version counter shows the masters were written from outside
         the step; after a write the counters cannot see -- through `p.data` or a raw
         pointer (ctypes, another library) -- the caller must call it before the next
         step() or eval forward."""
-        self.trunk.pack_weights(force=True)
+        for t in self.trunks:
+            t.pack_weights(force=True)
         self._packed_key = self._weights_key()
 
     def _sync_if_stale(self):
@@ -228,14 +242,15 @@ class RGBDGeometricTrainer:
              self.hp[5:6], self.seed, st)
         if self.pack_in_adamw:   # + the packed conv weights the next step's forward reads
             call("adamw_step_packed", self.arena.flat, self.arena.grad, self.m, self.v, self.partials, NPART, self.hp,
-                 self.norm, self.trunk.dt, self.trunk._desc_dev, self._jobs, self.n_jobs, st)
+                 self.norm, self.trunk.dt, self._pack_descs()[1], self._jobs, self.n_jobs, st)
         else:
             call("adamw_step", self.arena.flat, self.arena.grad, self.m, self.v, self.arena.numel, self.partials,
                  NPART, self.hp, self.norm, st)
 
     def _pack(self):
         if not self.pack_in_adamw:
-            self.trunk.pack_weights(force=True)
+            for t in self.trunks:
+                t.pack_weights(force=True)
 
     def step_eager(self, data):
         """One training step without graphs (reference order of operations)."""
@@ -260,10 +275,14 @@ class RGBDGeometricTrainer:
         self._forward_loss(*data)
         side = self._side_stream() if branch and POSE6D_HEAD_WGRAD_SIDE and self._head_wgrad_side else None
         dfeat = self._head_backward(wgrad_stream=side)
-        self.trunk.backward(dfeat, self.arena.grad_of)
+        self._trunk_backward(dfeat)
         if side is not None:
             torch.cuda.current_stream().wait_stream(side)
         self._optimizer()
+
+    def _trunk_backward(self, dfeat, on_conv_done=None):
+        """The trunks' backwards, in arena order, from what _head_backward returned."""
+        self.trunk.backward(dfeat, self.arena.grad_of, on_conv_done=on_conv_done)
 
     def _side_stream(self):
         if not hasattr(self, "_side"):
@@ -283,7 +302,7 @@ class RGBDGeometricTrainer:
             last = op.conv.bias if op.conv.bias is not None else op.conv.weight
             red.ready(self.arena.end_offset(last))
 
-        self.trunk.backward(dfeat, self.arena.grad_of, on_conv_done=on_conv)
+        self._trunk_backward(dfeat, on_conv_done=on_conv)
         red.finish()
 
     def _comm_stream(self):
@@ -352,7 +371,7 @@ class RGBDGeometricTrainer:
             self._pack()
             self._forward_loss(*data)
             dfeat = self._head_backward()
-            self.trunk.backward(dfeat, self.arena.grad_of, on_conv_done=on_conv)
+            self._trunk_backward(dfeat, on_conv_done=on_conv)
             st["g"].capture_end()
             segs.append((st["g"], (st["next"], len(ends))))
             opt = torch.cuda.CUDAGraph()
@@ -491,3 +510,73 @@ class RGBTrainer(RGBDGeometricTrainer):
         dfeat = self.head.backward(self.draw, self.arena.grad_of)
         # fan-in: both heads read the same feature -> dfeat = sum of their input gradients
         return self.trans_head.backward(self.dtrans, self.arena.grad_of, dx_out=dfeat, dx_accumulate=True)
+
+
+class RGBGeometricTrainer(RGBDGeometricTrainer):
+    """Fused, graph-captured training step for PoseNetRGBGeometric: the per-batch body of the
+    reference's scripts/training/train_rgb_geometric.py:97-110 (forward + PoseLoss(1, 10,
+    geodesic) + backward + clip_grad_norm_(1.0) + AdamW) on RGBDGeometricTrainer's machinery
+    with TWO trunks -- the ResNet50 under rot_head and the z-CNN under z_predictor -- in one
+    arena, one optimizer launch pair, one bucket plan.
+    data = (rgb, bbox_center, K, gt_rot, gt_trans); K is (B, 3, 3) or (3, 3).
+
+    Arena order = gradient-completion order: rot_head, z_predictor, the z-CNN, the ResNet50
+    (the small z-CNN's backward runs first, so the late, tail-capped DDP bucket is still the
+    ResNet's stem / layer1).  Both trunks read the same image: the ResNet engine converts it
+    to NHWC once and the z-CNN's stem reads that buffer (TrunkEngine.forward(input_from=)).
+    The head + loss is one pose6d_zgeo_head_loss launch: the translation is a differentiable
+    pinhole of z_predictor's (B, 1) output, whose gradient self.dz feeds z_predictor's
+    backward (dropout salts 1 and 2, as models/pose_net_rgb_geometric.py).  The AdamW launch
+    works from one descriptor table over both trunks' convs.  The captured step is one
+    chain: no side stream, whatever POSE6D_HEAD_WGRAD_SIDE says."""
+
+    _head_wgrad_side = False
+
+    def _build_trunks(self, model):
+        self.trunk = TrunkEngine(model.rgb_backbone, 3)
+        self.z_trunk = TrunkEngine(model.z_backbone, 3, kind="zcnn")
+        return [self.z_trunk, self.trunk]
+
+    def _build_heads(self, model):
+        self.head = HeadEngine(model.rot_head)
+        self.z_head = HeadEngine(model.z_predictor)
+        self.dz = torch.empty(self.B, 1, device=self.dev)
+        return self.head.params_in_grad_order() + self.z_head.params_in_grad_order()
+
+    def _pack_descs(self):
+        """Both trunks' pack tables as one (descriptor k of the job table indexes it), each
+        table's `start` -- its packed-element offset within its own table -- rebased onto
+        the tables before it; rebuilt when a trunk rebuilt its own."""
+        key = tuple(t._desc_ptrs for t in self.trunks)
+        if getattr(self, "_descs_key", None) != key:
+            recs, base = [], 0
+            for t in self.trunks:
+                r = t._desc_host.copy()
+                r["start"] += base
+                base += t._pack_total
+                recs.append(r)
+            host = np.concatenate(recs)
+            self._descs = (host, torch.from_numpy(host.view(np.uint8).copy()).to(self.dev))
+            self._descs_key = key
+        return self._descs
+
+    def _forward_loss(self, rgb, bbox, K, gt_rot, gt_trans):
+        st = stream()
+        feat = self.trunk.forward(rgb, True, pack=False)
+        raw = self.head.forward(feat, True, seed_dev=self.seed, salt=1)
+        zfeat = self.z_trunk.forward(rgb, True, pack=False, input_from=self.trunk)
+        z = self.z_head.forward(zfeat, True, seed_dev=self.seed, salt=2)
+        # normalise + pinhole(z) + PoseLoss fwd/bwd + pinhole / normalise bwd: one launch (the
+        # arithmetic of the rownorm_* / pinhole_z_* / pose_loss_* entry points)
+        call("zgeo_head_loss", raw, z, bbox, K, 1 if K.dim() == 3 else 0, gt_rot, gt_trans, self.B, self.wr, self.wt,
+             0, self.rot, self.trans, self.loss, self.draw, self.dz, st)
+        return raw
+
+    def _head_backward(self, wgrad_stream=None):
+        dfeat = self.head.backward(self.draw, self.arena.grad_of)
+        return dfeat, self.z_head.backward(self.dz, self.arena.grad_of)
+
+    def _trunk_backward(self, dfeat, on_conv_done=None):
+        dfeat, dzfeat = dfeat
+        self.z_trunk.backward(dzfeat, self.arena.grad_of, on_conv_done=on_conv_done)
+        self.trunk.backward(dfeat, self.arena.grad_of, on_conv_done=on_conv_done)

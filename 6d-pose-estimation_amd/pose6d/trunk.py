@@ -229,7 +229,7 @@ class TrunkEngine:
         self.B, self.dtype, self.dt, self.device = B, dtype, DTYPES[dtype], device
         e = lambda *s, dt=dtype: torch.empty(*s, device=device, dtype=dt)
         f32 = lambda *s: torch.empty(*s, device=device, dtype=torch.float32)
-        self.input.t = e(B, H, W, self.input.C)
+        self._own_input = self.input.t = e(B, H, W, self.input.C)
         ws_w, ws_bn, ws_sk = 0, 0, 0
         for op in self.ops:
             o = op.out
@@ -378,11 +378,14 @@ class TrunkEngine:
             self._pack_key = key
 
     # ------------------------------------------------------------ forward
-    def forward(self, x, training, pack=True, inference=False):
+    def forward(self, x, training, pack=True, inference=False, input_from=None):
         """x: (B, C, H, W) fp32 on device -> features (B, feat_dim) fp32 (engine buffer).
         Eval mode folds each BatchNorm into its conv's epilogue: such a forward keeps no
         backward state, so backward() after it raises (`inference` is accepted for the
-        autograd bridge; the trunk's eval forward is the same either way)."""
+        autograd bridge; the trunk's eval forward is the same either way).
+        input_from (another TrunkEngine whose last forward converted this same x): no
+        NCHW -> NHWC launch here -- this forward, and the backward that follows it, read
+        that engine's input buffer, which must match this engine's in shape and dtype."""
         require_device(x)
         B, C, H, W = x.shape
         if C != self.in_channels:
@@ -393,15 +396,25 @@ class TrunkEngine:
             self.pack_weights()
         st = stream()
         dt = self.dt
-        xf = x.detach()
-        if xf.dtype != torch.float32:
-            xf = xf.float()
-        if padw:
-            # odd-width bf16 input to a row-tap stem: one zero column on the right (exact:
-            # see _stem_pad_cols); torch does the copy, the trunk runs on the even width
-            xf = torch.nn.functional.pad(xf, (0, padw))
-        xf = xf.contiguous()
-        call("nchw_to_nhwc", dt, xf, self.input.t, B, C, H, W + padw, self.input.C, st)
+        if input_from is not None:
+            src = input_from.input.t if input_from._shape is not None else None
+            own = self._own_input
+            if src is None or src.shape != own.shape or src.dtype != own.dtype or src.device != own.device:
+                raise Pose6dError("TrunkEngine.forward: input_from's input buffer %s does not match this engine's %s"
+                                  % ("(none: no forward yet)" if src is None else (tuple(src.shape), src.dtype),
+                                     (tuple(own.shape), own.dtype)))
+            self.input.t = src
+        else:
+            self.input.t = self._own_input
+            xf = x.detach()
+            if xf.dtype != torch.float32:
+                xf = xf.float()
+            if padw:
+                # odd-width bf16 input to a row-tap stem: one zero column on the right (exact:
+                # see _stem_pad_cols); torch does the copy, the trunk runs on the even width
+                xf = torch.nn.functional.pad(xf, (0, padw))
+            xf = xf.contiguous()
+            call("nchw_to_nhwc", dt, xf, self.input.t, B, C, H, W + padw, self.input.C, st)
         # eval: the BN (running statistics) is known before the conv runs, so the conv's
         # epilogue applies BN (+ residual) + ReLU and stores the activation directly
         fold = not training and self.eval_fuse
@@ -655,7 +668,8 @@ class TrunkEngine:
                     else:
                         dx = src.g
                 if op.conv.bias is not None:   # before conv_done(op) can mark the bucket ready
-                    call("channel_sum", dt, dy, M, op.cout, grad_of(op.conv.bias), acc, st)
+                    call("channel_sum_ws", dt, dy, M, op.cout, grad_of(op.conv.bias), acc, self.ws_bn,
+                         self.ws_bn.numel(), st)
                 # data + weight gradient: one fused launch on the bf16 fast path
                 ws = ws_pp[slot]
                 dw = grad_of(op.conv.weight)

@@ -149,6 +149,19 @@ int pose6d_quat_head_loss(const float *raw, const float *trans, const float *gt_
                           float rot_weight, float trans_weight, int32_t rot_mode, int32_t norm_mode, float *rot,
                           float *loss, float *grad_raw, float *grad_trans, void *stream);
 
+/* PoseNetRGBGeometric's training-step head + loss in one launch: rot = raw / (||raw|| + 1e-8)
+ * (pose6d_rownorm_* mode 1, pose_net_rgb_geometric.py:75), trans = ((u - cx) z / fx,
+ * (v - cy) z / fy, z) from the predicted depth z [B] (no clamps: pose6d_pinhole_z_fwd's
+ * arithmetic, pose_net_rgb_geometric.py:93-109), loss = PoseLoss(rot, trans)
+ * (pose_loss.py:19-28) and its gradient for dloss = 1: grad_raw [B][4] (through the
+ * normalise) and grad_z [B] (sign(trans - gt) * trans_weight / (3 B) folded through the
+ * pinhole: pose6d_pinhole_z_bwd's formula).  rot, trans and loss are bit-identical to
+ * pose6d_rownorm_fwd + pose6d_pinhole_z_fwd + pose6d_pose_loss_fwd.  B > 0, rot_mode 0 / 1. */
+int pose6d_zgeo_head_loss(const float *raw, const float *z, const float *bbox_center, const float *K,
+                          int32_t K_batched, const float *gt_rot, const float *gt_trans, int64_t B,
+                          float rot_weight, float trans_weight, int32_t rot_mode, float *rot, float *trans,
+                          float *loss, float *grad_raw, float *grad_z, void *stream);
+
 /* ------------------------------------------------------------------------
  * Input crops -- replaces the per-sample body of LineMODDatasetRGBD.__getitem__
  * after the file reads (data/dataset_rgbd.py:104-206; dataset_rgb.py:95-145 for
@@ -539,6 +552,13 @@ int pose6d_bn_bwd(int32_t dtype, const void *dout, const void *out, const float 
 /* conv bias gradient: out[c] (+)= sum_m x[m][c] over an NHWC tensor of M pixels */
 int pose6d_channel_sum(int32_t dtype, const void *x, int64_t M, int32_t C, float *out, int32_t accumulate,
                        void *stream);
+/* the same sum in two passes (row-block partials in `workspace`, then one add per channel in
+ * block order: deterministic) -- for long tensors, where pose6d_channel_sum's one block per
+ * 64 channels is serial (32 channels x 400 K pixels: 23 ms against tens of microseconds).
+ * Any workspace size works (up to 512 * C floats are used); with room for fewer than two
+ * row blocks, or C not a power-of-two number of 16-byte chunks, it is pose6d_channel_sum. */
+int pose6d_channel_sum_ws(int32_t dtype, const void *x, int64_t M, int32_t C, float *out, int32_t accumulate,
+                          float *workspace, int64_t workspace_floats, void *stream);
 
 /* nn.MaxPool2d(k, s, p) on NHWC; argmax = window index (uint8) of the first max */
 int pose6d_maxpool_fwd(int32_t dtype, const void *x, void *y, uint8_t *argmax, int32_t N, int32_t H, int32_t W,
