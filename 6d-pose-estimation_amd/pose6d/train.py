@@ -4,7 +4,8 @@ i.e. the per-batch body of the reference's train() loop
 (scripts/training/train_rgbd_geometric.py:97-115), without autograd or host syncs.
 RGBTrainer (at the end) is the same step for PoseNetRGB's two heads
 (scripts/training/train_rgb.py:95-141), RGBGeometricTrainer for PoseNetRGBGeometric's two
-trunks (scripts/training/train_rgb_geometric.py:97-110).
+trunks (scripts/training/train_rgb_geometric.py:97-110), RGBDTrainer for PoseNetRGBD's two
+ResNet50s, fusion core and GELU heads (scripts/training/train_rgbd.py:97-110).
 
 MI355X design:
   * one flat fp32 arena for parameters / gradients / AdamW moments (the module's
@@ -40,6 +41,7 @@ import torch
 
 from ._lib import Pose6dError, call, query, stream
 from .dist import BucketReducer, plan_buckets
+from .fusion import FusionEngine
 from .head import HeadEngine
 from .trunk import TrunkEngine
 
@@ -580,3 +582,71 @@ class RGBGeometricTrainer(RGBDGeometricTrainer):
         dfeat, dzfeat = dfeat
         self.z_trunk.backward(dzfeat, self.arena.grad_of, on_conv_done=on_conv_done)
         self.trunk.backward(dfeat, self.arena.grad_of, on_conv_done=on_conv_done)
+
+
+class RGBDTrainer(RGBGeometricTrainer):
+    """Fused, graph-captured training step for PoseNetRGBD: the per-batch body of the
+    reference's scripts/training/train_rgbd.py:97-110 (forward + PoseLoss(1, 10, geodesic) +
+    backward + clip_grad_norm_(1.0) + AdamW) on RGBDGeometricTrainer's machinery with two
+    full-size ResNet50 trunks (rgb, and depth with its 1-channel stem padded to 4 channels),
+    the cross-modal fusion core, the fusion MLP and two GELU heads -- one arena, one optimizer
+    launch pair over RGBGeometricTrainer's two-trunk descriptor table, one bucket plan.
+    data = (rgb, depth, gt_rot, gt_trans), depth (B, 1, 224, 224).
+
+    Arena order = gradient-completion order: rot_head, trans_head, the fusion MLP, the fusion
+    core (out_proj, q_proj, k_proj | v_proj side by side, the two norms), the depth trunk,
+    the rgb trunk.  `fused` feeds both heads: the translation head's data-gradient GEMM adds
+    its input gradient onto the rotation head's (beta = 1), no add launch.  Dropout salts are
+    models/pose_net_rgbd.py's (3 fusion core, 4 fusion MLP, 5 rot_head, 6 trans_head), all on
+    the trainer's device seed.  The head + loss is one pose6d_quat_head_loss launch
+    (norm_mode 0, F.normalize); self.trans is the translation head's output.
+
+    fused_fusion=True: the fusion core runs FusionEngine(stacked=True) -- both LayerNorms in
+    one launch each way and k_proj / v_proj as one stacked Linear (5 + 8 entry-point calls);
+    False: the engine's 7-forward / 14-backward launch chain that the autograd path runs
+    (kept for A/B timing and tests).  The captured step is one chain: no side stream,
+    whatever POSE6D_HEAD_WGRAD_SIDE says."""
+
+    def __init__(self, model, batch, *args, fused_fusion=True, **kw):
+        self.fused_fusion = bool(fused_fusion)
+        super().__init__(model, batch, *args, **kw)
+
+    def _build_trunks(self, model):
+        self.trunk = TrunkEngine(model.rgb_backbone, 3)
+        self.depth_trunk = TrunkEngine(model.depth_backbone, 1)
+        return [self.depth_trunk, self.trunk]
+
+    def _build_heads(self, model):
+        self.head = HeadEngine(model.rot_head)
+        self.trans_head = HeadEngine(model.trans_head)
+        self.fusion_mlp = HeadEngine(model.fusion)
+        self.fusion = FusionEngine(model.cross_attention, model.rgb_norm, model.depth_norm,
+                                   stacked=self.fused_fusion)
+        return (self.head.params_in_grad_order() + self.trans_head.params_in_grad_order()
+                + self.fusion_mlp.params_in_grad_order() + self.fusion.params_in_grad_order())
+
+    def _forward_loss(self, rgb, depth, gt_rot, gt_trans):
+        st = stream()
+        rgb_feat = self.trunk.forward(rgb, True, pack=False)
+        depth_feat = self.depth_trunk.forward(depth, True, pack=False)
+        combined = self.fusion.forward(rgb_feat, depth_feat, True, seed_dev=self.seed, salt=3)
+        fused = self.fusion_mlp.forward(combined, True, seed_dev=self.seed, salt=4)
+        raw = self.head.forward(fused, True, seed_dev=self.seed, salt=5)
+        trans = self.trans_head.forward(fused, True, seed_dev=self.seed, salt=6)
+        # F.normalize + PoseLoss fwd/bwd + normalize bwd: one launch, as in RGBTrainer
+        call("quat_head_loss", raw, trans, gt_rot, gt_trans, self.B, self.wr, self.wt, 0, 0, self.rot, self.loss,
+             self.draw, self.dtrans, st)
+        self.trans = trans
+        return raw
+
+    def _head_backward(self, wgrad_stream=None):
+        dfused = self.head.backward(self.draw, self.arena.grad_of)
+        # fan-in: both heads read `fused` -> dfused = sum of their input gradients
+        dfused = self.trans_head.backward(self.dtrans, self.arena.grad_of, dx_out=dfused, dx_accumulate=True)
+        dcombined = self.fusion_mlp.backward(dfused, self.arena.grad_of)
+        return self.fusion.backward(dcombined, self.arena.grad_of)      # (d rgb_feat, d depth_feat)
+
+    def _trunk_backward(self, dfeat, on_conv_done=None):
+        d_rgb, d_depth = dfeat
+        self.depth_trunk.backward(d_depth, self.arena.grad_of, on_conv_done=on_conv_done)
+        self.trunk.backward(d_rgb, self.arena.grad_of, on_conv_done=on_conv_done)

@@ -639,6 +639,29 @@ int pose6d_layernorm_bwd(const float *dy, int64_t lddy, const float *dy2, int64_
                          const float *mean, const float *rstd, int32_t act, float p_drop, const uint8_t *mask,
                          float *dx, int64_t lddx, int32_t accumulate_dx, float *dgamma, float *dbeta,
                          int32_t accumulate, void *stream);
+/* Two independent plain LayerNorms (act 0, no dropout: rgb_norm / depth_norm,
+ * pose_net_rgbd.py:127-128) over (B, D) rows in ONE launch each way.  Side a and side b
+ * each have their own x / gamma / beta / eps / mean / rstd and their own output pointer
+ * and row stride; y2_* (optional, contiguous (B, D)) receives a second copy.  Forward:
+ * a grid of 2 B workgroups.  Backward: one grid of 2 B row workgroups (dx_* = the
+ * LayerNorm backward of dy_* + dy2_*, dy2_* optional, strides separate; dx is stored,
+ * never accumulated) followed by 2 ceil(D / 256) column workgroups (dgamma_* / dbeta_*,
+ * += when accumulate); dx, dgamma and dbeta of both sides are required.  Per row and
+ * per column the arithmetic is pose6d_layernorm_fwd / pose6d_layernorm_bwd's own (shared
+ * device functions): the results equal two separate calls bit for bit.  Every ld >= D;
+ * B == 0 returns POSE6D_OK. */
+int pose6d_layernorm_pair_fwd(const float *x_a, int64_t ldx_a, float *y_a, int64_t ldy_a, float *y2_a,
+                              const float *gamma_a, const float *beta_a, float eps_a, float *mean_a, float *rstd_a,
+                              const float *x_b, int64_t ldx_b, float *y_b, int64_t ldy_b, float *y2_b,
+                              const float *gamma_b, const float *beta_b, float eps_b, float *mean_b, float *rstd_b,
+                              int32_t B, int32_t D, void *stream);
+int pose6d_layernorm_pair_bwd(const float *dy_a, int64_t lddy_a, const float *dy2_a, int64_t lddy2_a,
+                              const float *x_a, int64_t ldx_a, const float *gamma_a, const float *beta_a,
+                              const float *mean_a, const float *rstd_a, float *dx_a, int64_t lddx_a, float *dgamma_a,
+                              float *dbeta_a, const float *dy_b, int64_t lddy_b, const float *dy2_b, int64_t lddy2_b,
+                              const float *x_b, int64_t ldx_b, const float *gamma_b, const float *beta_b,
+                              const float *mean_b, const float *rstd_b, float *dx_b, int64_t lddx_b, float *dgamma_b,
+                              float *dbeta_b, int32_t B, int32_t D, int32_t accumulate, void *stream);
 
 /* CrossModalAttention core (pose_net_rgbd.py:23-35): per sample b,
  *   attn = softmax((q_b k_b^T) * scale), q_b, k_b, v_b = (H, hd) views of rows
@@ -651,6 +674,19 @@ int pose6d_xattn_fwd(const float *q, const float *k, const float *v, float *out,
 int pose6d_xattn_bwd(const float *dout, const float *q, const float *k, const float *v, const float *probs,
                      const uint8_t *mask, int32_t B, int32_t H, int32_t hd, float scale, float p_drop, float *dq,
                      float *dk, float *dv, void *stream);
+/* The same kernels with element row strides (each >= H * hd) on q, k, v, out and, in the
+ * backward, on dout, q, k, v, dq, dk, dv: k and v (dk and dv) may be the two halves of one
+ * (B, 2 H hd) buffer, the output / input of a stacked K|V projection.  The contiguous
+ * entry points above call these with every stride H * hd.  probs and mask stay
+ * contiguous (B*H*H) and the dropout index stays b*H*H + i*H + j, so one seed and salt
+ * draw the same mask whatever the strides. */
+int pose6d_xattn_fwd_strided(const float *q, int64_t ldq, const float *k, int64_t ldk, const float *v, int64_t ldv,
+                             float *out, int64_t ldo, int32_t B, int32_t H, int32_t hd, float scale, float p_drop,
+                             const uint64_t *seed, uint64_t salt, float *probs, uint8_t *mask, void *stream);
+int pose6d_xattn_bwd_strided(const float *dout, int64_t lddo, const float *q, int64_t ldq, const float *k,
+                             int64_t ldk, const float *v, int64_t ldv, const float *probs, const uint8_t *mask,
+                             int32_t B, int32_t H, int32_t hd, float scale, float p_drop, float *dq, int64_t lddq,
+                             float *dk, int64_t lddk, float *dv, int64_t lddv, void *stream);
 
 /* ------------------------------------------------------------------------
  * Optimiser — clip_grad_norm_(params, max_norm) + AdamW.step() of the callers
