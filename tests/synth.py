@@ -132,6 +132,27 @@ def write_linemod_tree(root, n_frames=100, H=120, W=160, seed=0):
     return written
 
 
+def uniform01(seed, index):
+    """Host restatement of p6::uniform01 (csrc/common.h): the splitmix64 finaliser of
+    (seed, index) in wrapping uint64 arithmetic, its top 24 bits as a float32 in [0, 1).
+    `seed` is the 64-bit word the kernels use (their seed word ^ salt); `index` an
+    array of element indices."""
+    with np.errstate(over="ignore"):
+        i = np.asarray(index).astype(np.uint64)
+        z = np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF) + np.uint64(0x9E3779B97F4A7C15) * (i + np.uint64(1))
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    return (z >> np.uint64(40)).astype(np.float32) * np.float32(2.0 ** -24)
+
+
+def dropout_keep(seed, salt, index, p):
+    """The dropout mask every kernel documents: keep = uniform01(seed ^ salt, index) >= p
+    (uint8, 1 = kept), `index` the element's documented flat index."""
+    word = (int(seed) ^ int(salt)) & 0xFFFFFFFFFFFFFFFF
+    return (uniform01(word, index) >= np.float32(p)).astype(np.uint8)
+
+
 def xattn_weights(D, seed):
     """CrossModalAttention parameters from a seeded CPU generator (q, k, v, out
     projections: N(0, 1/D) weights, N(0, 0.01) biases), as the model_parts fixture
