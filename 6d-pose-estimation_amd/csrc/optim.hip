@@ -329,6 +329,7 @@ __global__ __launch_bounds__(kThreads) void adamw_packed_kernel(float* __restric
 
 extern "C" int pose6d_sumsq_partial(const float* g, int64_t n, float* partials, int32_t nparts, void* stream) {
   P6_CHECK_ARG(nparts > 0 && nparts <= 65535, "pose6d_sumsq_partial: bad nparts");
+  P6_CHECK_ARG(n <= 0 || (uintptr_t)g % 16 == 0, "pose6d_sumsq_partial: grad must be 16-byte aligned");
   sumsq_kernel<<<nparts, kThreads, 0, p6::stream_of(stream)>>>(g, n, partials, nullptr, nullptr);
   P6_LAUNCH_CHECK();
   return POSE6D_OK;
@@ -337,6 +338,7 @@ extern "C" int pose6d_sumsq_partial(const float* g, int64_t n, float* partials, 
 extern "C" int pose6d_sumsq_partial_step(const float* g, int64_t n, float* partials, int32_t nparts, float* step,
                                          int64_t* seed, void* stream) {
   P6_CHECK_ARG(nparts > 0 && nparts <= 65535, "pose6d_sumsq_partial_step: bad nparts");
+  P6_CHECK_ARG(n <= 0 || (uintptr_t)g % 16 == 0, "pose6d_sumsq_partial_step: grad must be 16-byte aligned");
   sumsq_kernel<<<nparts, kThreads, 0, p6::stream_of(stream)>>>(g, n, partials, step, seed);
   P6_LAUNCH_CHECK();
   return POSE6D_OK;

@@ -695,6 +695,7 @@ int pose6d_xattn_bwd_strided(const float *dout, int64_t lddo, const float *q, in
  *                corrections 1 - beta^t computed in-kernel), grad scale (applied to
  *                grad before the norm; 0 reads as 1 — the DDP trainer's 1/world),
  *                max_norm (<= 0: no clipping)}
+ * grad, param and both moment buffers must be 16-byte aligned (read as float4).
  * ---------------------------------------------------------------------- */
 int pose6d_sumsq_partial(const float *g, int64_t n, float *partials, int32_t nparts, void *stream);
 /* the same, and (each optional) step[0] += 1 (the hp[5] counter pose6d_adamw_step reads next) and
