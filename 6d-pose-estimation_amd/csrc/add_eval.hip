@@ -16,6 +16,8 @@
 //                      almost never takes its update branch; the first-index tie rule
 //                      is order-free, so the bits do not depend on the seeds.
 //   add_reduce_kernel  grid B: fixed-order fp64 means (deterministic), 0.1d test.
+//   val_append_kernel  one workgroup: the batch's per-sample results become rows of a
+//                      device-resident epoch table (the validation pass, pose6d.validate).
 //
 // Bit-exactness contract (pinned by tests/golden/add_loss.npz):
 // this file is built with -ffp-contract=off; the only fused ops are the explicit
@@ -337,6 +339,34 @@ __global__ __launch_bounds__(kThreads) void add_reduce_kernel(
   }
 }
 
+// pose6d_val_append: one batch's per-sample results (what add_reduce_kernel wrote) become
+// rows of the epoch table at the device-resident cursor state[0], so a replayed graph
+// appends without the host knowing the row.  ONE workgroup: every thread reads the cursor
+// before the barrier, thread 0 writes it after, and stream order does the rest (no atomics,
+// no inter-workgroup protocol).  A batch that does not fit writes no row and counts itself
+// in state[1].  The values are copied as they are (doubles; the int32 flags convert exactly).
+__global__ __launch_bounds__(kThreads) void val_append_kernel(
+    const double* __restrict__ add, const double* __restrict__ adds, const int32_t* __restrict__ valid,
+    const int32_t* __restrict__ correct, int B, double* __restrict__ table, int64_t capacity,
+    int64_t* __restrict__ state) {
+  const int64_t row0 = state[0];
+  const bool fits = row0 >= 0 && row0 <= capacity - (int64_t)B;
+  if (fits) {
+    for (int b = threadIdx.x; b < B; b += kThreads) {
+      double* r = table + 4 * (row0 + b);
+      r[0] = add[b];
+      r[1] = adds[b];
+      r[2] = (double)valid[b];
+      r[3] = (double)correct[b];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (fits) state[0] = row0 + B;
+    else state[1] += 1;
+  }
+}
+
 // ---------------------------------------------------------------- ADD loss backward
 // d loss / d (pred_rot, pred_trans) of ADDLoss.forward (add_loss.py:101-150):
 //   loss = (1 / count) sum_i mean_k ||Q_ik - G*_ik||,  Q = P R(q)^T + t,
@@ -494,6 +524,18 @@ extern "C" int pose6d_add_eval(const float* pred_rot, const float* pred_trans, c
   return pose6d_add_eval_nbr(pred_rot, pred_trans, gt_rot, gt_trans, obj_ids, B, points, off, npts, sym, diam,
                              n_slots, max_npts, nullptr, 0, min_dist, argmin, pt_add, add, adds, valid, correct,
                              stream);
+}
+
+extern "C" int pose6d_val_append(const double* add, const double* adds, const int32_t* valid, const int32_t* correct,
+                                 int64_t B, double* table, int64_t capacity, int64_t* state, void* stream) {
+  P6_CHECK_ARG(B >= 0 && B <= 65535, "pose6d_val_append: batch %lld out of range", (long long)B);
+  P6_CHECK_ARG(capacity >= 0, "pose6d_val_append: capacity %lld is negative", (long long)capacity);
+  if (B == 0) return POSE6D_OK;
+  P6_CHECK_ARG(add && adds && valid && correct && table && state, "pose6d_val_append: null pointer");
+  val_append_kernel<<<1, kThreads, 0, p6::stream_of(stream)>>>(add, adds, valid, correct, (int)B, table, capacity,
+                                                                state);
+  P6_LAUNCH_CHECK();
+  return POSE6D_OK;
 }
 
 extern "C" int pose6d_add_loss_bwd(const float* pred_rot, const float* pred_trans, const float* gt_rot,

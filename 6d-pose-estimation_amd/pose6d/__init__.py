@@ -5,6 +5,8 @@ Layers:
   ops       torch.autograd.Functions over the C ABI (no CPU fallback)
   trunk     ResNet50 trunk engine: NHWC activations, packed weights, fused BN
   train     whole-step trainer (fwd + loss + bwd + clip + AdamW), hipGraph-captured
+  validate  the epoch's validation pass on the trainer's engines (ADD metrics kept on the
+            device until the epoch ends) and the plateau lr schedule
   ddp       batch-sharded data parallel over RCCL
 The drop-in reference API lives in ../models (same module/class names).
 """

@@ -33,6 +33,7 @@ MI355X design:
     optimizer graph once every all-reduce has landed (a handful of host calls
     per step instead of ~300 eager launches).
 """
+import contextlib
 import math
 import os
 
@@ -231,6 +232,38 @@ class RGBDGeometricTrainer:
 
     def _head_backward(self, wgrad_stream=None):
         return self.head.backward(self.draw, self.arena.grad_of, wgrad_stream=wgrad_stream)
+
+    # ------------------------------------------------------------- validation forward
+    @contextlib.contextmanager
+    def _modules_in_eval(self):
+        """model.eval() for the engines that read their modules' flags (HeadEngine: BatchNorm1d
+        and Dropout, FusionEngine: the attention dropout), whatever the flags say, and the
+        flags put back afterwards (the tests train with single Dropouts switched off)."""
+        mods = list(self.model.modules())
+        flags = [m.training for m in mods]
+        self.model.eval()
+        try:
+            yield
+        finally:
+            for m, f in zip(mods, flags):
+                m.training = f
+
+    def _forward_eval(self, rgb, depth_raw, bbox, K, gt_rot=None, gt_trans=None):
+        """The eval-mode twin of _forward_loss on the trainer's own engines (pose6d.validate
+        runs it under model.eval() / no_grad's place in the reference's epoch,
+        train_rgbd_geometric.py:119-136): running statistics folded into the conv epilogues,
+        BatchNorm1d on running statistics, no dropout, the packed weights the AdamW launch
+        keeps current.  Predictions land in self.rot / self.trans, bit-identical to the
+        drop-in module's eval forward.  No loss, no gradient, no seed advance, no write to
+        anything a training step carries over; `data` is the training tuple (the ground
+        truth at its end is not read)."""
+        st = stream()
+        with self._modules_in_eval():
+            feat = self.trunk.forward(rgb, False, pack=False)
+            raw = self.head.forward(feat, False, inference=True)
+        call("rownorm_fwd", raw, self.rot, self.B, 4, 0, st)
+        call("pinhole_depth", depth_raw, depth_raw.shape[1], depth_raw.shape[2], bbox, K, 1 if K.dim() == 3 else 0,
+             self.B, self.trans, st)
 
     def _optimizer(self):
         st = stream()
@@ -513,6 +546,17 @@ class RGBTrainer(RGBDGeometricTrainer):
         # fan-in: both heads read the same feature -> dfeat = sum of their input gradients
         return self.trans_head.backward(self.dtrans, self.arena.grad_of, dx_out=dfeat, dx_accumulate=True)
 
+    def _forward_eval(self, rgb, gt_rot=None, gt_trans=None):
+        """RGBDGeometricTrainer._forward_eval for PoseNetRGB: self.trans is the translation
+        head's output as it is."""
+        st = stream()
+        with self._modules_in_eval():
+            feat = self.trunk.forward(rgb, False, pack=False)
+            raw = self.head.forward(feat, False, inference=True)
+            trans = self.trans_head.forward(feat, False, inference=True)
+        call("rownorm_fwd", raw, self.rot, self.B, 4, 0, st)
+        self.trans = trans
+
 
 class RGBGeometricTrainer(RGBDGeometricTrainer):
     """Fused, graph-captured training step for PoseNetRGBGeometric: the per-batch body of the
@@ -577,6 +621,19 @@ class RGBGeometricTrainer(RGBDGeometricTrainer):
     def _head_backward(self, wgrad_stream=None):
         dfeat = self.head.backward(self.draw, self.arena.grad_of)
         return dfeat, self.z_head.backward(self.dz, self.arena.grad_of)
+
+    def _forward_eval(self, rgb, bbox, K, gt_rot=None, gt_trans=None):
+        """RGBDGeometricTrainer._forward_eval for PoseNetRGBGeometric: raw / (||raw|| + 1e-8)
+        and the pinhole of z_predictor's output (the z-CNN reads the ResNet engine's NHWC
+        input, as in training)."""
+        st = stream()
+        with self._modules_in_eval():
+            feat = self.trunk.forward(rgb, False, pack=False)
+            raw = self.head.forward(feat, False, inference=True)
+            zfeat = self.z_trunk.forward(rgb, False, pack=False, input_from=self.trunk)
+            z = self.z_head.forward(zfeat, False, inference=True)
+        call("rownorm_fwd", raw, self.rot, self.B, 4, 1, st)
+        call("pinhole_z_fwd", z, bbox, K, 1 if K.dim() == 3 else 0, self.B, self.trans, st)
 
     def _trunk_backward(self, dfeat, on_conv_done=None):
         dfeat, dzfeat = dfeat
@@ -645,6 +702,28 @@ class RGBDTrainer(RGBGeometricTrainer):
         dfused = self.trans_head.backward(self.dtrans, self.arena.grad_of, dx_out=dfused, dx_accumulate=True)
         dcombined = self.fusion_mlp.backward(dfused, self.arena.grad_of)
         return self.fusion.backward(dcombined, self.arena.grad_of)      # (d rgb_feat, d depth_feat)
+
+    def _forward_eval(self, rgb, depth, gt_rot=None, gt_trans=None):
+        """RGBDGeometricTrainer._forward_eval for PoseNetRGBD.  The fusion core runs on an
+        unstacked FusionEngine over the same modules (a few (B, 2048) buffers, built on first
+        use): the stacked k | v GEMM of the training step sums in another order than the
+        drop-in module's separate projections, and validation must give that module's bits."""
+        st = stream()
+        fusion = self.fusion
+        if fusion.stacked:
+            if not hasattr(self, "_eval_fusion"):
+                self._eval_fusion = FusionEngine(self.model.cross_attention, self.model.rgb_norm,
+                                                 self.model.depth_norm, stacked=False)
+            fusion = self._eval_fusion
+        with self._modules_in_eval():
+            rgb_feat = self.trunk.forward(rgb, False, pack=False)
+            depth_feat = self.depth_trunk.forward(depth, False, pack=False)
+            combined = fusion.forward(rgb_feat, depth_feat, False)
+            fused = self.fusion_mlp.forward(combined, False, inference=True)
+            raw = self.head.forward(fused, False, inference=True)
+            trans = self.trans_head.forward(fused, False, inference=True)
+        call("rownorm_fwd", raw, self.rot, self.B, 4, 0, st)
+        self.trans = trans
 
     def _trunk_backward(self, dfeat, on_conv_done=None):
         d_rgb, d_depth = dfeat

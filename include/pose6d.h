@@ -83,6 +83,21 @@ int pose6d_add_eval_nbr(const float *pred_rot, const float *pred_trans, const fl
 int pose6d_add_neighbors(const float *points, const int32_t *off, const int32_t *npts, int32_t n_slots,
                          int32_t max_npts, int32_t K, uint16_t *nbr, void *stream);
 
+/* The validation pass's epoch table (the per-batch eval_metrics of the reference's
+ * training scripts, train_rgbd_geometric.py:119-146, kept on the device until the epoch
+ * ends): appends one batch's per-sample results at a device-resident cursor, so a
+ * replayed graph appends without the host knowing the row.
+ * add/adds/valid/correct [B]: the outputs of a pose6d_add_eval[_nbr] call.
+ * table [capacity][4] doubles, one row per sample: (add, adds, valid, correct).
+ * state int64[2] = {rows used, batches refused}.
+ * Writes rows state[0] .. state[0]+B-1, then state[0] += B.
+ * If state[0] + B > capacity: writes no row, leaves state[0], state[1] += 1.
+ * One workgroup; ordered against the calls before and after it by the stream alone.
+ * 0 <= B <= 65535, capacity >= 0; B == 0 touches nothing.  The values are stored exactly. */
+int pose6d_val_append(const double *add, const double *adds, const int32_t *valid,
+                      const int32_t *correct, int64_t B, double *table,
+                      int64_t capacity, int64_t *state, void *stream);
+
 /* Backward of ADDLoss.forward (add_loss.py:101-150) w.r.t. the predicted pose:
  * loss = mean over known samples of mean_k ||Q_k - G*_k|| (G* = G_k, or the
  * nearest ground-truth point for SYMMETRIC_OBJECT_IDS, taken from the `argmin`
