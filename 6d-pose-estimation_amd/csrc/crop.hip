@@ -15,6 +15,10 @@
 // Built with -ffp-contract=off: every fp32 op rounds like numpy / torch-CPU.
 // HBM-bound gather; algorithmic bytes per crop: <= 5 * crop^2 read (clipped to
 // the frame) + S^2 * (12 + 4 + 4) written.
+//
+// The *_indexed entry points draw the same crops from a device-resident frame store:
+// a device vector of sample indices picks table rows (frame, bbox, K, labels) and
+// through them the frames; the per-pixel body is shared (crop_pixel).
 #include <math.h>
 
 #include "common.h"
@@ -67,21 +71,22 @@ __device__ __forceinline__ void lin_coef(int d, int n, int S, bool clamp_edges, 
 
 __device__ __forceinline__ int fix_coef(float c) { return (int)rintf(c * (float)kCoefScale); }   // cvRound
 
-__global__ __launch_bounds__(kThreads) void crop_rgbd_kernel(
-    const uint8_t* __restrict__ rgb, int bgr, const uint16_t* __restrict__ depth, int H, int W,
-    const int32_t* __restrict__ bbox_orig, const int32_t* __restrict__ bbox_aug, const float* __restrict__ K, int S,
+// One output pixel of crop b (and, on its pix == 0 thread, the crop's centre and
+// intrinsics).  img / dimg: the sample's frame; ba / bo / k: the sample's jittered bbox,
+// original bbox and K rows.  Outputs are indexed by b.  Shared by the contiguous-batch
+// kernel and the frame-store (indexed) kernel, so the two cannot drift apart.
+__device__ __forceinline__ void crop_pixel(
+    int b, int pix, const uint8_t* __restrict__ img, int bgr, const uint16_t* __restrict__ dimg, int H, int W,
+    const int32_t* __restrict__ bo, const int32_t* __restrict__ ba, const float* __restrict__ k, int S,
     const float* __restrict__ mean_std, float* __restrict__ rgb_out, float* __restrict__ depth_out,
     float* __restrict__ depth_raw_out, float* __restrict__ center_out, float* __restrict__ K_out,
     uint8_t* __restrict__ u8_out) {
-  const int b = blockIdx.y;
-  const int pix = blockIdx.x * kThreads + threadIdx.x;
-  const CropGeom g = crop_geom(bbox_aug + 4 * b, H, W);
+  const CropGeom g = crop_geom(ba, H, W);
   const float scale32 = (float)((double)S / (double)g.n);   // np.float32(img_size / crop_size)
 
   if (pix == 0) {
     if (center_out) {
       // dataset_rgbd.py:105,148-156 (float32 arithmetic, NEP 50 weak Python scalars)
-      const int32_t* bo = bbox_orig + 4 * b;
       const float cgx = (float)((double)bo[0] + (double)bo[2] / 2.0);
       const float cgy = (float)((double)bo[1] + (double)bo[3] / 2.0);
       float ccx = (cgx + (float)g.pad_l) - (float)g.x1p;
@@ -93,7 +98,6 @@ __global__ __launch_bounds__(kThreads) void crop_rgbd_kernel(
     }
     if (K_out) {
       // dataset_rgbd.py:159-169
-      const float* k = K + 9 * b;
       float* ko = K_out + 9 * b;
       ko[0] = k[0] * scale32; ko[1] = 0.f; ko[2] = ((k[2] + (float)g.pad_l) - (float)g.x1p) * scale32;
       ko[3] = 0.f; ko[4] = k[4] * scale32; ko[5] = ((k[5] + (float)g.pad_t) - (float)g.y1p) * scale32;
@@ -103,9 +107,6 @@ __global__ __launch_bounds__(kThreads) void crop_rgbd_kernel(
   if (pix >= S * S) return;
   const int oy = pix / S, ox = pix - oy * S;
   const int n = g.n;
-  const int64_t HW = (int64_t)H * W;
-  const uint8_t* img = rgb + (int64_t)b * HW * 3;
-  const uint16_t* dimg = depth ? depth + (int64_t)b * HW : nullptr;
 
   // crop pixel (r, c) -> frame pixel (y1 + r, x1 + c); zero outside the frame
   auto in_frame = [&](int r, int c, int64_t& off) {
@@ -198,6 +199,100 @@ __global__ __launch_bounds__(kThreads) void crop_rgbd_kernel(
   }
 }
 
+__global__ __launch_bounds__(kThreads) void crop_rgbd_kernel(
+    const uint8_t* __restrict__ rgb, int bgr, const uint16_t* __restrict__ depth, int H, int W,
+    const int32_t* __restrict__ bbox_orig, const int32_t* __restrict__ bbox_aug, const float* __restrict__ K, int S,
+    const float* __restrict__ mean_std, float* __restrict__ rgb_out, float* __restrict__ depth_out,
+    float* __restrict__ depth_raw_out, float* __restrict__ center_out, float* __restrict__ K_out,
+    uint8_t* __restrict__ u8_out) {
+  const int b = blockIdx.y;
+  const int pix = blockIdx.x * kThreads + threadIdx.x;
+  const int64_t HW = (int64_t)H * W;
+  crop_pixel(b, pix, rgb + (int64_t)b * HW * 3, bgr, depth ? depth + (int64_t)b * HW : nullptr, H, W,
+             bbox_orig + 4 * b, bbox_aug + 4 * b, K + 9 * b, S, mean_std, rgb_out, depth_out, depth_raw_out,
+             center_out, K_out, u8_out);
+}
+
+// The tables and the store of the indexed entry points (device pointers).
+struct StoreTabs {
+  const uint8_t* rgb;
+  const uint16_t* depth;       // or nullptr
+  int64_t n_frames, n_samples;
+  const int32_t* frame_of;     // [n_samples]
+  const int32_t* bbox;         // [n_samples][4]
+  const float* K;              // [n_samples][9]
+  const float* center;         // [n_samples][2] or nullptr
+  const float* quat;           // [n_samples][4]
+  const float* trans;          // [n_samples][3]
+  const int64_t* obj_id;       // [n_samples]
+};
+
+struct LabelOuts {
+  float* quat;
+  float* trans;
+  int64_t* obj;
+  int32_t* status;
+};
+
+// Crop b of a batch drawn from a device-resident frame store: sample s = sample_idx[b]
+// (read here, at kernel time), frame frame_of[s].  Nothing is read through an index
+// before it has been range-checked: a bad sample or frame index zero-fills the crop's
+// outputs, sets obj_out to -1 and raises *status to b + 1.  Otherwise crop_pixel on the
+// sample's frame and table rows; the pix == 0 thread also gathers the labels (and, for
+// the RGB datasets, the original-image centre and K).
+__global__ __launch_bounds__(kThreads) void crop_rgbd_indexed_kernel(
+    StoreTabs t, int bgr, int H, int W, const int64_t* __restrict__ sample_idx, const int32_t* __restrict__ bbox_aug,
+    int S, const float* __restrict__ mean_std, float* __restrict__ rgb_out, float* __restrict__ depth_out,
+    float* __restrict__ depth_raw_out, float* __restrict__ center_out, float* __restrict__ K_out, LabelOuts lab,
+    uint8_t* __restrict__ u8_out) {
+  const int b = blockIdx.y;
+  const int pix = blockIdx.x * kThreads + threadIdx.x;
+  const int64_t s = sample_idx[b];
+  int64_t f = -1;
+  if (s >= 0 && s < t.n_samples) f = (int64_t)t.frame_of[s];
+  const int64_t plane = (int64_t)S * S;
+  if (f < 0 || f >= t.n_frames) {   // also: s out of range (f stayed -1)
+    if (pix == 0) {
+      if (center_out) center_out[2 * b] = center_out[2 * b + 1] = 0.f;
+      if (K_out)
+        for (int i = 0; i < 9; ++i) K_out[9 * b + i] = 0.f;
+      if (lab.quat)
+        for (int i = 0; i < 4; ++i) lab.quat[4 * b + i] = 0.f;
+      if (lab.trans)
+        for (int i = 0; i < 3; ++i) lab.trans[3 * b + i] = 0.f;
+      if (lab.obj) lab.obj[b] = -1;
+      if (lab.status) atomicMax(lab.status, b + 1);
+    }
+    if (pix >= plane) return;
+    if (u8_out) {
+      uint8_t* o = u8_out + ((int64_t)b * plane + pix) * 3;
+      o[0] = o[1] = o[2] = 0;
+    }
+    if (rgb_out)
+      for (int k = 0; k < 3; ++k) rgb_out[((int64_t)b * 3 + k) * plane + pix] = 0.f;
+    if (depth_raw_out) depth_raw_out[(int64_t)b * plane + pix] = 0.f;
+    if (depth_out) depth_out[(int64_t)b * plane + pix] = 0.f;
+    return;
+  }
+  if (pix == 0) {
+    if (lab.quat)
+      for (int i = 0; i < 4; ++i) lab.quat[4 * b + i] = t.quat[4 * s + i];
+    if (lab.trans)
+      for (int i = 0; i < 3; ++i) lab.trans[3 * b + i] = t.trans[3 * s + i];
+    if (lab.obj) lab.obj[b] = t.obj_id[s];
+    if (t.center) {   // dataset_rgb.py:96,139-141: the original-image centre and K, as stored
+      if (center_out) { center_out[2 * b] = t.center[2 * s]; center_out[2 * b + 1] = t.center[2 * s + 1]; }
+      if (K_out)
+        for (int i = 0; i < 9; ++i) K_out[9 * b + i] = t.K[9 * s + i];
+    }
+  }
+  const int64_t HW = (int64_t)H * W;
+  const int32_t* bo = t.bbox + 4 * s;
+  crop_pixel(b, pix, t.rgb + f * HW * 3, bgr, t.depth ? t.depth + f * HW : nullptr, H, W, bo,
+             bbox_aug ? bbox_aug + 4 * b : bo, t.K + 9 * s, S, mean_std, rgb_out, depth_out, depth_raw_out,
+             t.center ? nullptr : center_out, t.center ? nullptr : K_out, u8_out);
+}
+
 }  // namespace
 
 extern "C" int pose6d_crop_rgbd(const uint8_t* rgb, int32_t bgr, const uint16_t* depth, int32_t B, int32_t H,
@@ -213,6 +308,39 @@ extern "C" int pose6d_crop_rgbd(const uint8_t* rgb, int32_t bgr, const uint16_t*
   crop_rgbd_kernel<<<grid, kThreads, 0, p6::stream_of(stream)>>>(rgb, bgr, depth, H, W, bbox_orig, bbox_aug, K, S,
                                                                  mean_std, rgb_out, depth_out, depth_raw_out,
                                                                  center_out, K_out, nullptr);
+  P6_LAUNCH_CHECK();
+  return POSE6D_OK;
+}
+
+// The argument checks the two indexed entry points share (`fn`: the name in the message).
+#define P6_CHECK_INDEXED_ARGS(fn)                                                                                  \
+  P6_CHECK_ARG(rgb_store != nullptr && frame_of != nullptr && bbox != nullptr && K != nullptr && quat != nullptr && \
+                   trans != nullptr && obj_id != nullptr && sample_idx != nullptr,                                  \
+               fn ": rgb_store, the tables (frame_of, bbox, K, quat, trans, obj_id) and sample_idx are required");  \
+  P6_CHECK_ARG(B >= 0 && B <= 65535 && n_samples >= 0 && n_frames >= 0 && n_samples < (1ll << 31) &&                \
+                   n_frames < (1ll << 31) && H > 0 && W > 0 && S > 0 && (int64_t)S * S < (1ll << 31),               \
+               fn ": bad shape");                                                                                   \
+  P6_CHECK_ARG(K_out == nullptr || K != nullptr, fn ": K_out needs K");                                            \
+  P6_CHECK_ARG(center_out == nullptr || center_tab != nullptr || bbox != nullptr,                                  \
+               fn ": center_out needs center_tab or bbox")
+
+extern "C" int pose6d_crop_rgbd_indexed(const uint8_t* rgb_store, int32_t bgr, const uint16_t* depth_store,
+                                        int64_t n_frames, int32_t H, int32_t W, const int32_t* frame_of,
+                                        const int32_t* bbox, const float* K, const float* center_tab,
+                                        const float* quat, const float* trans, const int64_t* obj_id,
+                                        int64_t n_samples, const int64_t* sample_idx, const int32_t* bbox_aug,
+                                        int32_t B, int32_t S, const float* mean_std, float* rgb_out,
+                                        float* depth_out, float* depth_raw_out, float* center_out, float* K_out,
+                                        float* quat_out, float* trans_out, int64_t* obj_out, int32_t* status,
+                                        void* stream) {
+  P6_CHECK_INDEXED_ARGS("pose6d_crop_rgbd_indexed");
+  if (B == 0) return POSE6D_OK;
+  const StoreTabs t{rgb_store, depth_store, n_frames, n_samples, frame_of, bbox, K, center_tab, quat, trans, obj_id};
+  const LabelOuts lab{quat_out, trans_out, obj_out, status};
+  const dim3 grid(p6::ceil_div((int64_t)S * S, kThreads), B);
+  crop_rgbd_indexed_kernel<<<grid, kThreads, 0, p6::stream_of(stream)>>>(
+      t, bgr, H, W, sample_idx, bbox_aug, S, mean_std, rgb_out, depth_out, depth_raw_out, center_out, K_out, lab,
+      nullptr);
   P6_LAUNCH_CHECK();
   return POSE6D_OK;
 }
@@ -412,34 +540,18 @@ __global__ __launch_bounds__(kAugThreads) void augment_kernel(const uint8_t* __r
 
 }  // namespace
 
-extern "C" int64_t pose6d_crop_train_workspace(int32_t B, int32_t S) { return (int64_t)B * S * S * 3; }
+namespace {
 
-extern "C" int pose6d_crop_rgbd_train(const uint8_t* rgb, int32_t bgr, const uint16_t* depth, int32_t B, int32_t H,
-                                      int32_t W, const int32_t* bbox_orig, const int32_t* bbox_aug, const float* K,
-                                      int32_t S, const float* mean_std, float brightness, float contrast,
-                                      float saturation, float hue, float erase_p, float erase_scale_lo,
-                                      float erase_scale_hi, float erase_ratio_lo, float erase_ratio_hi,
-                                      uint64_t seed, uint8_t* workspace, float* rgb_out, float* depth_out,
-                                      float* depth_raw_out, float* center_out, float* K_out, float* params_out,
-                                      void* stream) {
-  P6_CHECK_ARG(rgb != nullptr && bbox_aug != nullptr && workspace != nullptr && rgb_out != nullptr,
-               "pose6d_crop_rgbd_train: rgb, bbox_aug, workspace and rgb_out are required");
-  P6_CHECK_ARG(B >= 0 && H > 0 && W > 0 && S > 0 && S <= 232, "pose6d_crop_rgbd_train: bad shape (S <= 232: the "
-               "crop must fit one workgroup's LDS)");
-  P6_CHECK_ARG(center_out == nullptr || bbox_orig != nullptr, "pose6d_crop_rgbd_train: center_out needs bbox_orig");
-  P6_CHECK_ARG(K_out == nullptr || K != nullptr, "pose6d_crop_rgbd_train: K_out needs K");
-  P6_CHECK_ARG(brightness >= 0.f && contrast >= 0.f && saturation >= 0.f && hue >= 0.f && hue <= 0.5f,
-               "pose6d_crop_rgbd_train: ColorJitter factors must be >= 0 (hue <= 0.5)");
-  P6_CHECK_ARG(erase_p >= 0.f && erase_p <= 1.f && erase_scale_lo <= erase_scale_hi && erase_ratio_lo > 0.f &&
-                   erase_ratio_lo <= erase_ratio_hi,
-               "pose6d_crop_rgbd_train: bad RandomErasing arguments");
-  if (B == 0) return POSE6D_OK;
-  hipStream_t s = p6::stream_of(stream);
-  const dim3 grid(p6::ceil_div((int64_t)S * S, kThreads), B);
-  crop_rgbd_kernel<<<grid, kThreads, 0, s>>>(rgb, bgr, depth, H, W, bbox_orig, bbox_aug, K, S, nullptr, nullptr,
-                                             depth_out, depth_raw_out, center_out, K_out, workspace);
-  P6_LAUNCH_CHECK();
-  // ColorJitter._check_input: value v -> [max(0, 1 - v), 1 + v] (hue: [-v, v]); 0 -> the op is off
+#define P6_CHECK_AUG_ARGS(fn)                                                                                   \
+  P6_CHECK_ARG(brightness >= 0.f && contrast >= 0.f && saturation >= 0.f && hue >= 0.f && hue <= 0.5f,           \
+               fn ": ColorJitter factors must be >= 0 (hue <= 0.5)");                                            \
+  P6_CHECK_ARG(erase_p >= 0.f && erase_p <= 1.f && erase_scale_lo <= erase_scale_hi && erase_ratio_lo > 0.f &&   \
+                   erase_ratio_lo <= erase_ratio_hi,                                                             \
+               fn ": bad RandomErasing arguments")
+
+// ColorJitter._check_input: value v -> [max(0, 1 - v), 1 + v] (hue: [-v, v]); 0 -> the op is off
+AugCfg aug_cfg(float brightness, float contrast, float saturation, float hue, float erase_p, float erase_scale_lo,
+               float erase_scale_hi, float erase_ratio_lo, float erase_ratio_hi) {
   AugCfg cfg;
   const float v[4] = {brightness, contrast, saturation, hue};
   for (int k = 0; k < 4; ++k) {
@@ -456,8 +568,67 @@ extern "C" int pose6d_crop_rgbd_train(const uint8_t* rgb, int32_t bgr, const uin
   cfg.scale_hi = erase_scale_hi;
   cfg.log_r_lo = logf(erase_ratio_lo);   // torch.log(torch.tensor(ratio)): float32
   cfg.log_r_hi = logf(erase_ratio_hi);
-  const int lds = S * S * 3;
-  augment_kernel<<<B, kAugThreads, lds, s>>>(workspace, S, mean_std, cfg, seed, rgb_out, params_out);
+  return cfg;
+}
+
+}  // namespace
+
+extern "C" int64_t pose6d_crop_train_workspace(int32_t B, int32_t S) { return (int64_t)B * S * S * 3; }
+
+extern "C" int pose6d_crop_rgbd_train(const uint8_t* rgb, int32_t bgr, const uint16_t* depth, int32_t B, int32_t H,
+                                      int32_t W, const int32_t* bbox_orig, const int32_t* bbox_aug, const float* K,
+                                      int32_t S, const float* mean_std, float brightness, float contrast,
+                                      float saturation, float hue, float erase_p, float erase_scale_lo,
+                                      float erase_scale_hi, float erase_ratio_lo, float erase_ratio_hi,
+                                      uint64_t seed, uint8_t* workspace, float* rgb_out, float* depth_out,
+                                      float* depth_raw_out, float* center_out, float* K_out, float* params_out,
+                                      void* stream) {
+  P6_CHECK_ARG(rgb != nullptr && bbox_aug != nullptr && workspace != nullptr && rgb_out != nullptr,
+               "pose6d_crop_rgbd_train: rgb, bbox_aug, workspace and rgb_out are required");
+  P6_CHECK_ARG(B >= 0 && H > 0 && W > 0 && S > 0 && S <= 232, "pose6d_crop_rgbd_train: bad shape (S <= 232: the "
+               "crop must fit one workgroup's LDS)");
+  P6_CHECK_ARG(center_out == nullptr || bbox_orig != nullptr, "pose6d_crop_rgbd_train: center_out needs bbox_orig");
+  P6_CHECK_ARG(K_out == nullptr || K != nullptr, "pose6d_crop_rgbd_train: K_out needs K");
+  P6_CHECK_AUG_ARGS("pose6d_crop_rgbd_train");
+  if (B == 0) return POSE6D_OK;
+  hipStream_t s = p6::stream_of(stream);
+  const dim3 grid(p6::ceil_div((int64_t)S * S, kThreads), B);
+  crop_rgbd_kernel<<<grid, kThreads, 0, s>>>(rgb, bgr, depth, H, W, bbox_orig, bbox_aug, K, S, nullptr, nullptr,
+                                             depth_out, depth_raw_out, center_out, K_out, workspace);
+  P6_LAUNCH_CHECK();
+  const AugCfg cfg = aug_cfg(brightness, contrast, saturation, hue, erase_p, erase_scale_lo, erase_scale_hi,
+                             erase_ratio_lo, erase_ratio_hi);
+  augment_kernel<<<B, kAugThreads, S * S * 3, s>>>(workspace, S, mean_std, cfg, seed, rgb_out, params_out);
+  P6_LAUNCH_CHECK();
+  return POSE6D_OK;
+}
+
+extern "C" int pose6d_crop_rgbd_train_indexed(
+    const uint8_t* rgb_store, int32_t bgr, const uint16_t* depth_store, int64_t n_frames, int32_t H, int32_t W,
+    const int32_t* frame_of, const int32_t* bbox, const float* K, const float* center_tab, const float* quat,
+    const float* trans, const int64_t* obj_id, int64_t n_samples, const int64_t* sample_idx, const int32_t* bbox_aug,
+    int32_t B, int32_t S, const float* mean_std, float brightness, float contrast, float saturation, float hue,
+    float erase_p, float erase_scale_lo, float erase_scale_hi, float erase_ratio_lo, float erase_ratio_hi,
+    uint64_t seed, uint8_t* workspace, float* rgb_out, float* depth_out, float* depth_raw_out, float* center_out,
+    float* K_out, float* quat_out, float* trans_out, int64_t* obj_out, float* params_out, int32_t* status,
+    void* stream) {
+  P6_CHECK_INDEXED_ARGS("pose6d_crop_rgbd_train_indexed");
+  P6_CHECK_ARG(workspace != nullptr && rgb_out != nullptr,
+               "pose6d_crop_rgbd_train_indexed: workspace and rgb_out are required");
+  P6_CHECK_ARG(S <= 232, "pose6d_crop_rgbd_train_indexed: bad shape (S <= 232: the crop must fit one workgroup's "
+               "LDS)");
+  P6_CHECK_AUG_ARGS("pose6d_crop_rgbd_train_indexed");
+  if (B == 0) return POSE6D_OK;
+  hipStream_t s = p6::stream_of(stream);
+  const StoreTabs t{rgb_store, depth_store, n_frames, n_samples, frame_of, bbox, K, center_tab, quat, trans, obj_id};
+  const LabelOuts lab{quat_out, trans_out, obj_out, status};
+  const dim3 grid(p6::ceil_div((int64_t)S * S, kThreads), B);
+  crop_rgbd_indexed_kernel<<<grid, kThreads, 0, s>>>(t, bgr, H, W, sample_idx, bbox_aug, S, nullptr, nullptr,
+                                                     depth_out, depth_raw_out, center_out, K_out, lab, workspace);
+  P6_LAUNCH_CHECK();
+  const AugCfg cfg = aug_cfg(brightness, contrast, saturation, hue, erase_p, erase_scale_lo, erase_scale_hi,
+                             erase_ratio_lo, erase_ratio_hi);
+  augment_kernel<<<B, kAugThreads, S * S * 3, s>>>(workspace, S, mean_std, cfg, seed, rgb_out, params_out);
   P6_LAUNCH_CHECK();
   return POSE6D_OK;
 }

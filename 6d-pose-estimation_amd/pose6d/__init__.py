@@ -7,6 +7,7 @@ Layers:
   train     whole-step trainer (fwd + loss + bwd + clip + AdamW), hipGraph-captured
   validate  the epoch's validation pass on the trainer's engines (ADD metrics kept on the
             device until the epoch ends) and the plateau lr schedule
+  store     device-resident frame store + epoch feeder (index-gathered training crops)
   ddp       batch-sharded data parallel over RCCL
 The drop-in reference API lives in ../models (same module/class names).
 """

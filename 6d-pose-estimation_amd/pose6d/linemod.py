@@ -94,6 +94,7 @@ class LineMODSet:
                 continue
             self._load_folder(obj_folder)
         self._crop = CropRGBD(img_size)
+        self._store = None
 
     def _load_folder(self, obj_folder):
         """dataset_rgbd.py:36-82 / dataset_rgb.py:35-78 for one object folder."""
@@ -133,14 +134,27 @@ class LineMODSet:
         ids = torch.tensor([it["obj_id"] for it in items], dtype=torch.long)
         return q, t, ids
 
+    def cache(self, device="cuda", workers=None):
+        """Decode every frame once into a device-resident FrameStore (pose6d/store.py)
+        and keep it: batch() then draws from the store -- the same tensors, bit for
+        bit, without the per-batch decode and upload.  Returns the store."""
+        from .store import FrameStore
+        self._store = FrameStore.from_linemod(self, device, workers)
+        return self._store
+
     def batch(self, indices, device, rng=np.random):
         """The collated DataLoader batch for samples `indices`, on `device`:
         RGB-D (rgb, depth, depth_raw, quaternion, translation, obj_id, bbox_center,
         camera_matrix) as dataset_rgbd.py:206; RGB (rgb, quaternion, translation,
         obj_id, bbox_center, camera_matrix) as dataset_rgb.py:147."""
+        indices = list(indices)
         items = [self.all_data[i] for i in indices]
         if not items:
             raise Pose6dError("LineMODSet.batch: empty index list")
+        if self._store is not None:   # cache(): `device` is the store's
+            idx = np.asarray(indices, np.int64)
+            ba = jitter_bboxes(self._store.host_bbox[idx], self.rgbd, rng) if self.augment_bbox else None
+            return self._store.crop(idx, ba)
         rgbs = [load_rgb(it["img_path"]) for it in items]
         shape = rgbs[0].shape
         if any(r.shape != shape for r in rgbs):

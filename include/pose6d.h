@@ -217,6 +217,56 @@ int pose6d_crop_rgbd_train(const uint8_t *rgb, int32_t bgr, const uint16_t *dept
                            float erase_ratio_hi, uint64_t seed, uint8_t *workspace, float *rgb_out, float *depth_out,
                            float *depth_raw_out, float *center_out, float *K_out, float *params_out, void *stream);
 
+/* ----------------------------------------------------------------------
+ * The same crops drawn by index from a device-resident frame store: one launch turns
+ * B sample indices into the B model inputs AND labels of the reference's collated
+ * batch (dataset_rgbd.py:206 / dataset_rgb.py:147).  The per-pixel arithmetic is
+ * pose6d_crop_rgbd's own body.
+ * Store: rgb_store [n_frames][H][W][3] uint8, depth_store [n_frames][H][W] uint16 or
+ * NULL (= zeros); all offsets into it are 64-bit.  Per-sample tables, n_samples rows,
+ * device: frame_of int32 (the sample's frame), bbox [.][4] int32 (x, y, w, h, before
+ * the jitter), K [.][9], quat [.][4], trans [.][3], obj_id int64, and center_tab
+ * [.][2] or NULL.  center_tab != NULL selects the RGB datasets' outputs: center_out and
+ * K_out are plain gathers of center_tab and K (the original-image centre and
+ * intrinsics, dataset_rgb.py:96,139-141); NULL: the crop-adjusted values of
+ * pose6d_crop_rgbd, from the table's bbox and K.
+ * Batch: sample_idx [B] int64, DEVICE memory, read at kernel time (a captured launch
+ * follows later writes to it); bbox_aug [B][4] int32 device (the jittered boxes, row
+ * b for crop b) or NULL (= the table's bbox).  B <= 65535.
+ * Outputs (each may be NULL): those of pose6d_crop_rgbd plus quat_out [B][4],
+ * trans_out [B][3], obj_out [B] int64, copied exactly from the tables.
+ * Bad indices cannot fault: a sample_idx[b] outside [0, n_samples) reads nothing from
+ * the tables or the store, a frame_of value outside [0, n_frames) nothing from the
+ * store; that crop's outputs are zeros, obj_out[b] = -1, and *status (one device
+ * int32, may be NULL; the caller zeroes it) is raised to b + 1 by atomicMax -- zero
+ * after any number of launches means every index was good.  B == 0 launches nothing.
+ * ---------------------------------------------------------------------- */
+int pose6d_crop_rgbd_indexed(const uint8_t *rgb_store, int32_t bgr, const uint16_t *depth_store, int64_t n_frames,
+                             int32_t H, int32_t W, const int32_t *frame_of, const int32_t *bbox, const float *K,
+                             const float *center_tab, const float *quat, const float *trans, const int64_t *obj_id,
+                             int64_t n_samples, const int64_t *sample_idx, const int32_t *bbox_aug, int32_t B,
+                             int32_t S, const float *mean_std, float *rgb_out, float *depth_out,
+                             float *depth_raw_out, float *center_out, float *K_out, float *quat_out,
+                             float *trans_out, int64_t *obj_out, int32_t *status, void *stream);
+
+/* pose6d_crop_rgbd_train on the indexed crops: the indexed crop into the uint8
+ * workspace (pose6d_crop_train_workspace(B, S) bytes), then the train transform,
+ * unchanged -- the same seed on the same resolved frames and boxes gives
+ * pose6d_crop_rgbd_train's bits and params_out.  rgb_out is required, S <= 232.  A
+ * crop with a bad index is transformed from an all-zero uint8 crop (its rgb_out is
+ * defined but not zero); its other outputs and *status are as above. */
+int pose6d_crop_rgbd_train_indexed(const uint8_t *rgb_store, int32_t bgr, const uint16_t *depth_store,
+                                   int64_t n_frames, int32_t H, int32_t W, const int32_t *frame_of,
+                                   const int32_t *bbox, const float *K, const float *center_tab, const float *quat,
+                                   const float *trans, const int64_t *obj_id, int64_t n_samples,
+                                   const int64_t *sample_idx, const int32_t *bbox_aug, int32_t B, int32_t S,
+                                   const float *mean_std, float brightness, float contrast, float saturation,
+                                   float hue, float erase_p, float erase_scale_lo, float erase_scale_hi,
+                                   float erase_ratio_lo, float erase_ratio_hi, uint64_t seed, uint8_t *workspace,
+                                   float *rgb_out, float *depth_out, float *depth_raw_out, float *center_out,
+                                   float *K_out, float *quat_out, float *trans_out, int64_t *obj_out,
+                                   float *params_out, int32_t *status, void *stream);
+
 /* ------------------------------------------------------------------------
  * ResNet50 trunk — replaces torchvision.models.resnet50 children[:-1] as
  * wrapped by every model (pose_net_rgb.py:18-20, pose_net_rgb_geometric.py:18-20,
