@@ -19,6 +19,10 @@
 // The *_indexed entry points draw the same crops from a device-resident frame store:
 // a device vector of sample indices picks table rows (frame, bbox, K, labels) and
 // through them the frames; the per-pixel body is shared (crop_pixel).
+//
+// pose6d_crop_detections is the inference scripts' flavour of the same crop
+// (scripts/inference/inference_rgbd_geometric.py:110-182): N detector boxes (x1, y1, x2, y2)
+// over F frames, depth resized as float32, centre and intrinsics in double with one cast.
 #include <math.h>
 
 #include "common.h"
@@ -75,6 +79,12 @@ __device__ __forceinline__ int fix_coef(float c) { return (int)rintf(c * (float)
 // intrinsics).  img / dimg: the sample's frame; ba / bo / k: the sample's jittered bbox,
 // original bbox and K rows.  Outputs are indexed by b.  Shared by the contiguous-batch
 // kernel and the frame-store (indexed) kernel, so the two cannot drift apart.
+// kFloatDepth (compile time; false keeps the dataset flavour's code as it was): the
+// inference scripts' depth, resized as float32 (cv2.resize(crop_depth.astype(np.float32)),
+// inference_rgbd_geometric.py:142) -- the 16U branch's coefficients and mul + add without
+// the rounding to whole millimetres and the saturation; exact 2x: (a + b + c + d) * 0.25f,
+// exact for uint16 inputs in any order.
+template <bool kFloatDepth>
 __device__ __forceinline__ void crop_pixel(
     int b, int pix, const uint8_t* __restrict__ img, int bgr, const uint16_t* __restrict__ dimg, int H, int W,
     const int32_t* __restrict__ bo, const int32_t* __restrict__ ba, const float* __restrict__ k, int S,
@@ -129,7 +139,8 @@ __device__ __forceinline__ void crop_pixel(
   };
 
   int outc[3];
-  int dval;
+  int dval = 0;
+  float dvalf = 0.f;   // kFloatDepth: the unrounded depth in mm
   if (n == 2 * S) {
     // exact 2x downscale: cv::resize switches INTER_LINEAR to INTER_AREA (2x2 mean)
     const int r = 2 * oy, c = 2 * ox;
@@ -137,7 +148,11 @@ __device__ __forceinline__ void crop_pixel(
     px3(r, c, a); px3(r, c + 1, bq); px3(r + 1, c, cq); px3(r + 1, c + 1, dq);
 #pragma unroll
     for (int k = 0; k < 3; ++k) outc[k] = (a[k] + bq[k] + cq[k] + dq[k] + 2) >> 2;
-    dval = (pxd(r, c) + pxd(r, c + 1) + pxd(r + 1, c) + pxd(r + 1, c + 1) + 2) >> 2;
+    if constexpr (kFloatDepth) {
+      dvalf = (float)(pxd(r, c) + pxd(r, c + 1) + pxd(r + 1, c) + pxd(r + 1, c + 1)) * 0.25f;
+    } else {
+      dval = (pxd(r, c) + pxd(r, c + 1) + pxd(r + 1, c) + pxd(r + 1, c + 1) + 2) >> 2;
+    }
   } else {
     int sx, sy;
     float fx, fy;
@@ -166,8 +181,12 @@ __device__ __forceinline__ void crop_pixel(
       const float d00 = (float)pxd(r0, c0), d10 = (float)pxd(r1, c0);
       const float h0 = edge ? d00 * 1.f : d00 * fa0 + (float)pxd(r0, c1) * fx;
       const float h1 = edge ? d10 * 1.f : d10 * fa0 + (float)pxd(r1, c1) * fx;
-      const float v = rintf(h0 * fb0 + h1 * fy);
-      dval = v < 0.f ? 0 : (v > 65535.f ? 65535 : (int)v);
+      if constexpr (kFloatDepth) {
+        dvalf = h0 * fb0 + h1 * fy;
+      } else {
+        const float v = rintf(h0 * fb0 + h1 * fy);
+        dval = v < 0.f ? 0 : (v > 65535.f ? 65535 : (int)v);
+      }
     } else {
       dval = 0;
     }
@@ -189,7 +208,7 @@ __device__ __forceinline__ void crop_pixel(
     }
   }
   // dataset_rgbd.py:176-186
-  const float raw = (float)dval / 1000.f;
+  const float raw = (kFloatDepth ? dvalf : (float)dval) / 1000.f;
   if (depth_raw_out) depth_raw_out[(int64_t)b * plane + pix] = raw;
   if (depth_out) {
     float dn = (raw - 0.1f) / 1.5f;
@@ -208,7 +227,7 @@ __global__ __launch_bounds__(kThreads) void crop_rgbd_kernel(
   const int b = blockIdx.y;
   const int pix = blockIdx.x * kThreads + threadIdx.x;
   const int64_t HW = (int64_t)H * W;
-  crop_pixel(b, pix, rgb + (int64_t)b * HW * 3, bgr, depth ? depth + (int64_t)b * HW : nullptr, H, W,
+  crop_pixel<false>(b, pix, rgb + (int64_t)b * HW * 3, bgr, depth ? depth + (int64_t)b * HW : nullptr, H, W,
              bbox_orig + 4 * b, bbox_aug + 4 * b, K + 9 * b, S, mean_std, rgb_out, depth_out, depth_raw_out,
              center_out, K_out, u8_out);
 }
@@ -288,12 +307,111 @@ __global__ __launch_bounds__(kThreads) void crop_rgbd_indexed_kernel(
   }
   const int64_t HW = (int64_t)H * W;
   const int32_t* bo = t.bbox + 4 * s;
-  crop_pixel(b, pix, t.rgb + f * HW * 3, bgr, t.depth ? t.depth + f * HW : nullptr, H, W, bo,
+  crop_pixel<false>(b, pix, t.rgb + f * HW * 3, bgr, t.depth ? t.depth + f * HW : nullptr, H, W, bo,
              bbox_aug ? bbox_aug + 4 * b : bo, t.K + 9 * s, S, mean_std, rgb_out, depth_out, depth_raw_out,
              t.center ? nullptr : center_out, t.center ? nullptr : K_out, u8_out);
 }
 
+// The small per-detection outputs of the inference path.
+struct DetOuts {
+  float* center_crop;   // [N][2]
+  float* K_crop;        // [N][9]
+  float* center_img;    // [N][2]
+  float* K_img;         // [N][9]
+  int32_t* status;
+};
+
+// Detection b of N over F frames: the per-detection body of the reference's inference
+// scripts (inference_rgbd_geometric.py:110-182) up to the model call.  The box is
+// (x1, y1, x2, y2), read here at kernel time; its square crop is crop_geom on
+// (x1, y1, x2 - x1, y2 - y1) (:118-135: (x1 + x2) / 2 and x1 + (x2 - x1) / 2 are both
+// exact in double).  The pixels are crop_pixel's with the float depth flavour; the centre
+// and intrinsics run in double and round once (:145-167), unlike the dataset's float32.
+__global__ __launch_bounds__(kThreads) void crop_detections_kernel(
+    const uint8_t* __restrict__ frames, int bgr, const uint16_t* __restrict__ depth, int F, int H, int W,
+    const int32_t* __restrict__ frame_of, const int32_t* __restrict__ boxes, const double* __restrict__ K,
+    int K_per_frame, int S, const float* __restrict__ mean_std, int k_mode, float* __restrict__ rgb_out,
+    float* __restrict__ depth_out, float* __restrict__ depth_raw_out, DetOuts o) {
+  const int b = blockIdx.y;
+  const int pix = blockIdx.x * kThreads + threadIdx.x;
+  const int f = frame_of ? frame_of[b] : 0;
+  const int64_t plane = (int64_t)S * S;
+  if (f < 0 || f >= F) {   // nothing is read through the bad index
+    if (pix == 0) {
+      if (o.center_crop) o.center_crop[2 * b] = o.center_crop[2 * b + 1] = 0.f;
+      if (o.center_img) o.center_img[2 * b] = o.center_img[2 * b + 1] = 0.f;
+      for (int i = 0; i < 9; ++i) {
+        if (o.K_crop) o.K_crop[9 * b + i] = 0.f;
+        if (o.K_img) o.K_img[9 * b + i] = 0.f;
+      }
+      if (o.status) atomicMax(o.status, b + 1);
+    }
+    if (pix >= plane) return;
+    if (rgb_out)
+      for (int k = 0; k < 3; ++k) rgb_out[((int64_t)b * 3 + k) * plane + pix] = 0.f;
+    if (depth_raw_out) depth_raw_out[(int64_t)b * plane + pix] = 0.f;
+    if (depth_out) depth_out[(int64_t)b * plane + pix] = 0.f;
+    return;
+  }
+  const int32_t* bx = boxes + 4 * b;
+  const int32_t bb[4] = {bx[0], bx[1], bx[2] - bx[0], bx[3] - bx[1]};
+  if (pix == 0) {
+    const CropGeom g = crop_geom(bb, H, W);
+    const double* k = K + (K_per_frame ? 9 * (int64_t)f : 0);
+    const double c_x = ((double)bx[0] + (double)bx[2]) / 2.0, c_y = ((double)bx[1] + (double)bx[3]) / 2.0;
+    const double scale = (double)S / (double)g.n;
+    if (o.center_crop) {   // :145-153: double, one cast, then the clip on the float32 array
+      const float ccx = (float)(((c_x + (double)g.pad_l) - (double)(g.x1 + g.pad_l)) * scale);
+      const float ccy = (float)(((c_y + (double)g.pad_t) - (double)(g.y1 + g.pad_t)) * scale);
+      o.center_crop[2 * b] = fminf(fmaxf(ccx, 0.f), (float)(S - 1));
+      o.center_crop[2 * b + 1] = fminf(fmaxf(ccy, 0.f), (float)(S - 1));
+    }
+    if (o.K_crop) {
+      // k_mode 0, :156-167: the script subtracts the UNPADDED origin after adding the pad,
+      // pad_l * scale more than k_mode 1, the dataset's (cx + pad_l - (x1 + pad_l)) =
+      // (cx - x1) * scale (dataset_rgbd.py:159-169) that the model was trained on
+      const double ox = k_mode ? k[2] - (double)g.x1 : (k[2] + (double)g.pad_l) - (double)g.x1;
+      const double oy = k_mode ? k[5] - (double)g.y1 : (k[5] + (double)g.pad_t) - (double)g.y1;
+      float* ko = o.K_crop + 9 * b;
+      ko[0] = (float)(k[0] * scale); ko[1] = 0.f; ko[2] = (float)(ox * scale);
+      ko[3] = 0.f; ko[4] = (float)(k[4] * scale); ko[5] = (float)(oy * scale);
+      ko[6] = 0.f; ko[7] = 0.f; ko[8] = 1.f;
+    }
+    if (o.center_img) {   // inference_rgb_geometric.py:105-106
+      o.center_img[2 * b] = (float)c_x;
+      o.center_img[2 * b + 1] = (float)c_y;
+    }
+    if (o.K_img)
+      for (int i = 0; i < 9; ++i) o.K_img[9 * b + i] = (float)k[i];
+  }
+  const int64_t HW = (int64_t)H * W;
+  crop_pixel<true>(b, pix, frames + (int64_t)f * HW * 3, bgr, depth ? depth + (int64_t)f * HW : nullptr, H, W, bb, bb,
+                   nullptr, S, mean_std, rgb_out, depth_out, depth_raw_out, nullptr, nullptr, nullptr);
+}
+
 }  // namespace
+
+extern "C" int pose6d_crop_detections(const uint8_t* frames, int32_t bgr, const uint16_t* depth, int32_t F, int32_t H,
+                                      int32_t W, const int32_t* frame_of, const int32_t* boxes_xyxy, int32_t N,
+                                      const double* K, int32_t K_per_frame, int32_t S, const float* mean_std,
+                                      int32_t k_mode, float* rgb_out, float* depth_out, float* depth_raw_out,
+                                      float* center_crop_out, float* K_crop_out, float* center_img_out,
+                                      float* K_img_out, int32_t* status, void* stream) {
+  P6_CHECK_ARG(frames != nullptr && boxes_xyxy != nullptr, "pose6d_crop_detections: frames and boxes_xyxy are required");
+  P6_CHECK_ARG(N >= 0 && N <= 65535 && F > 0 && H > 0 && W > 0 && S > 0 && (int64_t)S * S < (1ll << 31),
+               "pose6d_crop_detections: bad shape");
+  P6_CHECK_ARG((K_crop_out == nullptr && K_img_out == nullptr) || K != nullptr,
+               "pose6d_crop_detections: K_crop_out / K_img_out need K");
+  P6_CHECK_ARG(k_mode == 0 || k_mode == 1, "pose6d_crop_detections: k_mode is 0 (script) or 1 (dataset)");
+  if (N == 0) return POSE6D_OK;
+  const DetOuts o{center_crop_out, K_crop_out, center_img_out, K_img_out, status};
+  const dim3 grid(p6::ceil_div((int64_t)S * S, kThreads), N);
+  crop_detections_kernel<<<grid, kThreads, 0, p6::stream_of(stream)>>>(frames, bgr, depth, F, H, W, frame_of,
+                                                                       boxes_xyxy, K, K_per_frame, S, mean_std, k_mode,
+                                                                       rgb_out, depth_out, depth_raw_out, o);
+  P6_LAUNCH_CHECK();
+  return POSE6D_OK;
+}
 
 extern "C" int pose6d_crop_rgbd(const uint8_t* rgb, int32_t bgr, const uint16_t* depth, int32_t B, int32_t H,
                                 int32_t W, const int32_t* bbox_orig, const int32_t* bbox_aug, const float* K,

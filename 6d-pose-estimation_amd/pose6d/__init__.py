@@ -8,7 +8,10 @@ Layers:
   validate  the epoch's validation pass on the trainer's engines (ADD metrics kept on the
             device until the epoch ends) and the plateau lr schedule
   store     device-resident frame store + epoch feeder (index-gathered training crops)
+  infer     detection-to-pose inference: detector boxes -> crops -> eval forward -> projected
+            3D boxes, one hipGraph per detection-count bucket
   ddp       batch-sharded data parallel over RCCL
 The drop-in reference API lives in ../models (same module/class names).
 """
 from ._lib import Pose6dError, load  # noqa: F401
+from .infer import DEFAULT_K, CropDetections, PoseEstimator, load_mesh_corners  # noqa: F401

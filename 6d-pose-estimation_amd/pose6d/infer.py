@@ -1,0 +1,521 @@
+"""Detection-to-pose inference: what the reference's scripts/inference/inference_*.py do
+around the model, on the device.
+
+The scripts take a frame and a detector's boxes and, per detection, (1) cut a square
+crop x1.2 around the box, resize it to 224 and build the model inputs
+(inference_rgbd_geometric.py:110-182), (2) run the model, (3) for the RGB and RGBD
+models replace the predicted x, y by the box centre's ray at the predicted z
+(inference_rgb.py:99-104, inference_rgbd.py:159-164) and (4) project the object's 3D box
+and axes with the original intrinsics (utils/visualization.py:8-32,
+utils/mesh_utils.py:7-53).  Here:
+
+  CropDetections   (1) for all N detections of F frames in ONE launch
+                   (pose6d_crop_detections);
+  PoseEstimator    (1) -> eval forward of one of the four drop-in models -> (3) + (4) in
+                   one fp64 launch (pose6d_pose_project), replayed from one hipGraph per
+                   detection-count bucket;
+  load_mesh_corners / DEFAULT_K   the host helpers the scripts import.
+
+This is NOT CropRGBD on a detector box.  The scripts differ from the training dataset
+(data/dataset_rgbd.py) in three ways, all kept:
+  * depth is resized as float32 (no rounding to whole millimetres);
+  * the crop centre and intrinsics run in Python double and round to float32 once
+    (the dataset computes them in float32);
+  * the script's cx_crop = (cx + pad_l - crop_x1) * scale subtracts the UNPADDED crop
+    origin after adding the pad, pad_l * scale more than the dataset's (cx - crop_x1) *
+    scale on a box that hangs over the left edge (likewise at the top).  The models were
+    trained on the dataset's value: `dataset_intrinsics=True` feeds them that instead.
+
+No detector is built (YOLO stays out of scope: DESIGN.md); boxes come from the caller.
+"""
+import os
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from ._lib import Pose6dError, call, require_device, stream
+from .data import IMAGENET_MEAN, IMAGENET_STD
+
+# utils/camera.py:8-12 (float64)
+DEFAULT_K = np.array([[572.4114, 0.0, 325.2611], [0.0, 573.57043, 242.04899], [0.0, 0.0, 1.0]], dtype=np.float64)
+
+BUCKETS = (1, 2, 4, 8, 16, 32)
+N_POINTS = 12   # 8 box corners, origin, x / y / z axis tips
+
+# inputs of the four model kinds and whether the scripts correct the translation by the
+# box centre (inference_rgb.py:99-104, inference_rgbd.py:159-164) -- the two geometric
+# models compute a metric translation themselves
+_KINDS = {
+    "PoseNetRGB": (lambda c: (c.rgb,), True),
+    "PoseNetRGBD": (lambda c: (c.rgb, c.depth), True),
+    "PoseNetRGBGeometric": (lambda c: (c.rgb, c.center_img, c.K_img), False),
+    "PoseNetRGBDGeometric": (lambda c: (c.rgb, c.depth, c.depth_raw, c.center_crop, c.K_crop), False),
+}
+
+
+def load_mesh_corners(mesh_dir, obj_id_str):
+    """The 8 corners (metres) of an object's robust bounding box, as
+    utils/mesh_utils.py:7-53: vertices of the ASCII `obj_<id>.ply` in mm -> m, those
+    0.3 m or more from the origin dropped, the box spanned by the 1st and 99th
+    percentile per axis; corner order (min, min, min), (max, min, min), (max, max, min),
+    (min, max, min), then the same four at max z.  None for a missing mesh or one whose
+    vertices are all outliers."""
+    path = os.path.join(mesh_dir, f"obj_{obj_id_str}.ply")
+    if not os.path.exists(path):
+        return None
+    rows, body = [], False
+    with open(path, "r") as f:
+        for line in f:
+            if not body:
+                body = "end_header" in line
+                continue
+            v = line.split()
+            if len(v) >= 3:   # vertex lines (and, as in the reference, face lines: "3 i j k")
+                rows.append((float(v[0]), float(v[1]), float(v[2])))
+    verts = np.array(rows, dtype=np.float64).reshape(-1, 3) / 1000.0
+    verts = verts[np.linalg.norm(verts, axis=1) < 0.3]
+    if len(verts) == 0:
+        return None
+    lo = np.percentile(verts, 1, axis=0)
+    hi = np.percentile(verts, 99, axis=0)
+    sel = ((0, 0, 0), (1, 0, 0), (1, 1, 0), (0, 1, 0), (0, 0, 1), (1, 0, 1), (1, 1, 1), (0, 1, 1))
+    ends = (lo, hi)
+    return np.array([[ends[s[a]][a] for a in range(3)] for s in sel])
+
+
+def _host_boxes(boxes):
+    """Host boxes -> (N, 4) int64 numpy, floats truncated toward zero as the scripts'
+    map(int, box.xyxy[0]); empty or inverted boxes are refused."""
+    if isinstance(boxes, torch.Tensor):
+        boxes = boxes.numpy()
+    a = np.asarray(boxes)
+    if a.size == 0:
+        return np.zeros((0, 4), np.int64)
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise Pose6dError(f"boxes must be (N, 4) (x1, y1, x2, y2), got {a.shape}")
+    if not np.issubdtype(a.dtype, np.integer):
+        if not np.all(np.isfinite(a)):
+            raise Pose6dError("boxes must be finite")
+        a = np.trunc(a.astype(np.float64))
+    if np.any(np.abs(a) >= 2 ** 30):
+        raise Pose6dError("box coordinates must be below 2^30")
+    a = a.astype(np.int64)
+    bad = np.nonzero((a[:, 2] <= a[:, 0]) | (a[:, 3] <= a[:, 1]))[0]
+    if len(bad):
+        raise Pose6dError(f"box {int(bad[0])} is empty or inverted (x2 <= x1 or y2 <= y1): {a[bad[0]].tolist()}")
+    return a
+
+
+def _host_frame_of(frame_of, N, F):
+    a = np.asarray(frame_of.numpy() if isinstance(frame_of, torch.Tensor) else frame_of).astype(np.int64).reshape(-1)
+    if a.shape[0] != N:
+        raise Pose6dError(f"frame_of must have one entry per box ({N}), got {a.shape[0]}")
+    bad = np.nonzero((a < 0) | (a >= F))[0]
+    if len(bad):
+        raise Pose6dError(f"frame_of[{int(bad[0])}] = {int(a[bad[0]])} is outside [0, {F})")
+    return a
+
+
+def _is_dev(t):
+    return isinstance(t, torch.Tensor) and t.is_cuda
+
+
+def _k_dev(K, dev):
+    """K (3, 3) / (9,) or (F, 3, 3) / (F, 9) -> (float64 device tensor, K_per_frame)."""
+    t = K.detach() if isinstance(K, torch.Tensor) else torch.from_numpy(np.asarray(K, dtype=np.float64))
+    t = t.to(device=dev, dtype=torch.float64)
+    if t.numel() == 9 and t.dim() <= 2:
+        return t.reshape(9).contiguous(), 0
+    if t.dim() >= 2 and t[0].numel() == 9:
+        return t.reshape(t.shape[0], 9).contiguous(), 1
+    raise Pose6dError(f"K must be (3, 3) or (F, 3, 3), got {tuple(t.shape)}")
+
+
+DetectionCrops = namedtuple("DetectionCrops", "rgb depth depth_raw center_crop K_crop center_img K_img")
+
+
+class CropDetections:
+    """N detector boxes over F frames -> the model inputs, one pose6d_crop_detections launch.
+
+    __call__(frames, depth, boxes, frame_of=None, K=DEFAULT_K, out=None)
+      frames (F, H, W, 3) or (H, W, 3) uint8 device tensor (RGB; BGR with bgr=True);
+      depth (F, H, W) / (H, W) uint16 mm (int16 / int32 are converted) or None (zeros);
+      boxes (N, 4) (x1, y1, x2, y2): a host list / array / CPU tensor -- int, or float
+      truncated toward zero as the scripts' map(int, box.xyxy[0]); empty or inverted
+      boxes are refused -- or an int32 device tensor, used as it is and read at kernel
+      time; frame_of: N frame indices (a host sequence is range-checked here; a device
+      int32 tensor is checked by the kernel: see check()), None = all on frame 0;
+      K: (3, 3) or (F, 3, 3), taken as float64.
+    Returns DetectionCrops(rgb (N,3,S,S), depth (N,1,S,S), depth_raw (N,S,S),
+    center_crop (N,2), K_crop (N,3,3), center_img (N,2), K_img (N,3,3)), fp32.
+    dataset_intrinsics=False: K_crop is the script's (inference_rgbd_geometric.py:156-167);
+    True: the dataset's (dataset_rgbd.py:159-169), which the models were trained on (the
+    module docstring has the difference).
+    """
+
+    def __init__(self, img_size=224, normalize=True, bgr=False, dataset_intrinsics=False, mean=IMAGENET_MEAN,
+                 std=IMAGENET_STD):
+        self.img_size = int(img_size)
+        self.normalize = normalize
+        self.bgr = bgr
+        self.dataset_intrinsics = bool(dataset_intrinsics)
+        self._ms = torch.tensor(list(mean) + list(std), dtype=torch.float32)
+        self._ms_dev = {}
+        self._status = {}
+
+    def _mean_std(self, dev):
+        if not self.normalize:
+            return None
+        t = self._ms_dev.get(dev)
+        if t is None:
+            t = self._ms_dev[dev] = self._ms.to(dev)
+        return t
+
+    def _status_of(self, dev):
+        t = self._status.get(dev)
+        if t is None:
+            t = self._status[dev] = torch.zeros(1, dtype=torch.int32, device=dev)
+        return t
+
+    def empty_outputs(self, N, dev):
+        S = self.img_size
+        e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
+        return DetectionCrops(e(N, 3, S, S), e(N, 1, S, S), e(N, S, S), e(N, 2), e(N, 3, 3), e(N, 2), e(N, 3, 3))
+
+    def __call__(self, frames, depth, boxes, frame_of=None, K=DEFAULT_K, out=None):
+        require_device(frames, depth)
+        if frames.dim() == 3:
+            frames = frames[None]
+            depth = depth[None] if depth is not None and depth.dim() == 2 else depth
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+            raise Pose6dError(f"CropDetections: frames must be (F, H, W, 3) uint8, got {tuple(frames.shape)} "
+                              f"{frames.dtype}")
+        F, H, W, _ = frames.shape
+        dev = frames.device
+        if depth is not None:
+            if tuple(depth.shape) != (F, H, W):
+                raise Pose6dError(f"CropDetections: depth must be (F, H, W) = {(F, H, W)}, got {tuple(depth.shape)}")
+            if depth.dtype != torch.uint16:
+                depth = depth.to(torch.int32).clamp_(0, 65535).to(torch.uint16)
+            depth = depth.contiguous()
+        if _is_dev(boxes):
+            if boxes.dim() != 2 or boxes.shape[1] != 4:
+                raise Pose6dError(f"CropDetections: boxes must be (N, 4), got {tuple(boxes.shape)}")
+            bx = boxes.to(torch.int32).contiguous()   # a float tensor truncates toward zero
+        else:
+            bx = torch.from_numpy(_host_boxes(boxes).astype(np.int32)).to(dev)
+        N = bx.shape[0]
+        if frame_of is None:
+            fo = None
+        elif _is_dev(frame_of):
+            fo = frame_of.to(torch.int32).contiguous()
+            if fo.numel() != N:
+                raise Pose6dError(f"CropDetections: frame_of must have one entry per box ({N}), got {fo.numel()}")
+        else:
+            fo = torch.from_numpy(_host_frame_of(frame_of, N, F).astype(np.int32)).to(dev)
+        Kd, per_frame = K if isinstance(K, tuple) else _k_dev(K, dev)
+        if per_frame and Kd.shape[0] != F:
+            raise Pose6dError(f"CropDetections: per-frame K must have {F} rows, got {Kd.shape[0]}")
+        if out is None:
+            out = self.empty_outputs(N, dev)
+        call("crop_detections", frames.contiguous(), int(self.bgr), depth, F, H, W, fo, bx, N, Kd, per_frame,
+             self.img_size, self._mean_std(dev), int(self.dataset_intrinsics), *out, self._status_of(dev), stream())
+        return out
+
+    def check(self):
+        """Read the status word of every launch since the last check and reset it; raise
+        if a device-side frame_of entry was outside [0, F) (that detection's outputs are
+        zeros).  One host sync."""
+        for st in self._status.values():
+            v = int(st.item())
+            if v:
+                st.zero_()
+                raise Pose6dError(f"CropDetections.check: frame_of[{v - 1}] was outside the frames given (that "
+                                  f"detection's outputs are zeros)")
+
+
+def pose_project(quat, trans, K, obj, corners, boxes=None, frame_of=None, axis_scale=0.1, out=None):
+    """pose6d_pose_project on device tensors: quat (N, 4) fp32 (x, y, z, w), trans (N, 3)
+    fp32, K float64 (3, 3) / (F, 3, 3) (or _k_dev's pair), obj (N,) int64 rows of corners
+    (n_obj, 8, 3) float64; boxes (N, 4) int32 (x1, y1, x2, y2) switches the bbox-centre
+    translation correction on; frame_of (N,) int32 picks K's row.
+    Returns (trans (N, 3) f64, points (N, 12, 2) f64, pixels (N, 12, 2) i64, valid (N,) u8)."""
+    require_device(quat, trans, obj, corners, boxes, frame_of)
+    dev = quat.device
+    N = quat.shape[0]
+    Kd, per_frame = K if isinstance(K, tuple) else _k_dev(K, dev)
+    F = Kd.shape[0] if per_frame else 1
+    q = quat.detach().to(torch.float32).contiguous()
+    t = trans.detach().to(torch.float32).contiguous()
+    if q.shape != (N, 4) or t.shape != (N, 3) or obj.numel() != N:
+        raise Pose6dError("pose_project: quat (N, 4), trans (N, 3) and obj (N,) must agree")
+    c = corners.to(torch.float64).contiguous()
+    if c.dim() != 3 or c.shape[1:] != (8, 3):
+        raise Pose6dError(f"pose_project: corners must be (n_obj, 8, 3), got {tuple(c.shape)}")
+    bx = boxes.to(torch.int32).contiguous() if boxes is not None else None
+    fo = frame_of.to(torch.int32).contiguous() if frame_of is not None else None
+    if out is None:
+        out = (torch.empty(N, 3, device=dev, dtype=torch.float64),
+               torch.empty(N, N_POINTS, 2, device=dev, dtype=torch.float64),
+               torch.empty(N, N_POINTS, 2, device=dev, dtype=torch.int64),
+               torch.empty(N, device=dev, dtype=torch.uint8))
+    call("pose_project", q, t, bx, Kd, per_frame, fo, F, obj.to(torch.int64).contiguous(), c, c.shape[0],
+         float(axis_scale), N, *out, stream())
+    return out
+
+
+class PoseResult:
+    """Poses of N detections.  quat (N, 4) / trans (N, 3): the model's fp32 outputs;
+    trans_cam (N, 3) f64: the translation the projection used (bbox-centre corrected for the
+    RGB and RGBD models, else trans); points (N, 12, 2) f64 and their truncation pixels
+    (N, 12, 2) i64 -- box2d = pixels[:, :8] (project_points of the 8 corners), axes2d =
+    pixels[:, 8:] (origin, x, y, z tips: draw_axes); valid (N,) bool: False (rows zero)
+    for a class without a mesh or a zero quaternion.
+    From a PoseEstimator these are views of its output buffer, valid until its next call:
+    .cpu() (one device-to-host copy) or .clone() keeps them."""
+
+    _FIELDS = (("quat", torch.float32, (4,)), ("trans", torch.float32, (3,)), ("trans_cam", torch.float64, (3,)),
+               ("points", torch.float64, (N_POINTS, 2)), ("pixels", torch.int64, (N_POINTS, 2)),
+               ("valid", torch.uint8, ()))
+
+    def __init__(self, buf, bucket, n):
+        self._buf, self._bucket, self.n = buf, bucket, n
+        off = 0
+        for name, dt, shape in self._FIELDS:
+            cnt = bucket * int(np.prod(shape, dtype=np.int64))
+            nbytes = cnt * torch.empty((), dtype=dt).element_size()
+            setattr(self, "_" + name, buf[off:off + nbytes].view(dt).view(bucket, *shape))
+            off += (nbytes + 7) // 8 * 8
+
+    @classmethod
+    def nbytes(cls, bucket):
+        off = 0
+        for _, dt, shape in cls._FIELDS:
+            off += (bucket * int(np.prod(shape, dtype=np.int64)) * torch.empty((), dtype=dt).element_size() + 7) // 8 * 8
+        return off
+
+    quat = property(lambda s: s._quat[:s.n])
+    trans = property(lambda s: s._trans[:s.n])
+    trans_cam = property(lambda s: s._trans_cam[:s.n])
+    points = property(lambda s: s._points[:s.n])
+    pixels = property(lambda s: s._pixels[:s.n])
+    box2d = property(lambda s: s._pixels[:s.n, :8])
+    axes2d = property(lambda s: s._pixels[:s.n, 8:])
+    valid = property(lambda s: s._valid[:s.n].bool())
+
+    def cpu(self):
+        return PoseResult(self._buf.cpu(), self._bucket, self.n)
+
+    def clone(self):
+        return PoseResult(self._buf.clone(), self._bucket, self.n)
+
+
+class _Bucket:
+    """The static buffers and (graph=True) the captured graph of one (detections bucket,
+    depth present) pair."""
+
+    def __init__(self, B, dev, cropper):
+        self.B = B
+        self.boxes = torch.zeros(B, 4, dtype=torch.int32, device=dev)
+        self.frame_of = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.obj = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.crops = cropper.empty_outputs(B, dev)
+        self.out = torch.zeros(PoseResult.nbytes(B), dtype=torch.uint8, device=dev)
+        self.res = PoseResult(self.out, B, B)
+        self.engines = {}    # this bucket's own engines: their buffers are sized by the batch
+        self.graph = None
+
+
+class PoseEstimator:
+    """Frame(s) + detector boxes -> poses and projected 3D boxes, on the device.
+
+    model: one of the four drop-in modules (PoseNetRGB, PoseNetRGBD, PoseNetRGBGeometric,
+    PoseNetRGBDGeometric) in eval mode, on the device.  Its kind decides the inputs the
+    forward gets and whether the bbox-centre translation correction applies, as the four
+    inference scripts do.  corners: (n_obj, 8, 3) array, or a dict {key: (8, 3) or None}
+    (load_mesh_corners' results; a None is an object without a mesh).  class_to_obj: dict
+    detector class -> corners key / row (None: the class is the key); a class without
+    corners gives valid = False.  K: (3, 3) float64 for every frame, or (max_frames, 3, 3).
+
+    __call__(rgb, depth, boxes, classes, frame_of=None): rgb (H, W, 3) or (F, H, W, 3)
+    uint8 (host array or device tensor), F <= max_frames; depth (H, W) / (F, H, W) uint16
+    or None; boxes / classes / frame_of: N host entries (boxes as CropDetections takes
+    them).  Returns a PoseResult.  The N detections are padded to the next of 1, 2, 4, 8,
+    16, 32 by repeating detection 0, with and without a graph (so both run the same
+    launches and agree bit for bit); N = 0 returns empty tensors without a launch, N >
+    max_detections raises.
+    graph=True: frames, boxes and indices are copied into static buffers and ONE hipGraph
+    per (bucket, depth present) replays crop -> eval forward -> projection.  Each bucket
+    owns its engines (activation buffers and packed weights are sized per batch), so a
+    graph's pointers stay valid while other buckets run.
+    Weights: packed copies are synchronised on construction and on refresh(); call
+    refresh() after writing the model's weights (a replay runs no Python that could notice).
+    The model stays usable on its own: the estimator swaps a bucket's engines in around
+    each of its calls and restores the model's own afterwards.
+    """
+
+    def __init__(self, model, corners, K=DEFAULT_K, class_to_obj=None, max_detections=32, max_frames=1, graph=True,
+                 dataset_intrinsics=False, img_size=224, bgr=False, axis_scale=0.1):
+        kind = type(model).__name__
+        if kind not in _KINDS:
+            raise Pose6dError(f"PoseEstimator: model must be one of {sorted(_KINDS)}, got {kind}")
+        if model.training:
+            raise Pose6dError("PoseEstimator: the model is in training mode; call model.eval() first "
+                              "(inference uses the BatchNorm running statistics and no dropout)")
+        p = next(model.parameters())
+        if not p.is_cuda:
+            raise Pose6dError("PoseEstimator: the model must be on the ROCm device")
+        if not 1 <= int(max_detections) <= BUCKETS[-1]:
+            raise Pose6dError(f"PoseEstimator: max_detections must be in [1, {BUCKETS[-1]}]")
+        self.model, self.kind = model, kind
+        self._inputs, self.corrects_translation = _KINDS[kind]
+        self.device = p.device
+        self.max_detections, self.max_frames = int(max_detections), int(max_frames)
+        self.graph = bool(graph)
+        self.axis_scale = float(axis_scale)
+        self.cropper = CropDetections(img_size, True, bgr, dataset_intrinsics)
+        if isinstance(corners, dict):
+            keys = [k for k, v in corners.items() if v is not None]
+            tab = np.stack([np.asarray(corners[k], np.float64).reshape(8, 3) for k in keys]) if keys else \
+                np.zeros((0, 8, 3))
+            self._row = {k: i for i, k in enumerate(keys)}
+        else:
+            tab = np.asarray(corners, np.float64)
+            if tab.ndim != 3 or tab.shape[1:] != (8, 3):
+                raise Pose6dError(f"PoseEstimator: corners must be (n_obj, 8, 3), got {tab.shape}")
+            self._row = {i: i for i in range(tab.shape[0])}
+        self.corners = torch.from_numpy(np.ascontiguousarray(tab)).to(self.device)
+        self.class_to_obj = class_to_obj
+        self._K = _k_dev(K, self.device)
+        if self._K[1] and self._K[0].shape[0] != self.max_frames:
+            raise Pose6dError(f"PoseEstimator: per-frame K must have max_frames = {self.max_frames} rows")
+        self._frames = self._depth = None
+        self._buckets = {}
+        self._param_ptrs = self._ptrs()
+        self.refresh()
+
+    def _ptrs(self):
+        return tuple(t.data_ptr() for t in list(self.model.parameters()) + list(self.model.buffers()))
+
+    def refresh(self):
+        """Take over weights written since construction (or the last refresh): re-pack the
+        compute-dtype conv weights of every bucket's engines.  If a parameter or buffer
+        moved in memory (model.to(), a re-assigned Parameter) the captured graphs and the
+        engines are dropped and rebuilt on the next call."""
+        if self.model.training:
+            raise Pose6dError("PoseEstimator.refresh: the model is in training mode")
+        ptrs = self._ptrs()
+        if ptrs != self._param_ptrs:
+            self._param_ptrs = ptrs
+            self._buckets = {}
+            return self
+        for bk in self._buckets.values():
+            own, self.model._p6_engines = self.model._p6_engines, bk.engines
+            try:
+                self.model.sync_weights()
+            finally:
+                self.model._p6_engines = own
+        return self
+
+    def check(self):
+        """Read and reset the crop kernel's status word (raises on a bad frame index)."""
+        self.cropper.check()
+
+    def _objs(self, classes, N):
+        c = np.asarray(classes.cpu().numpy() if isinstance(classes, torch.Tensor) else classes).reshape(-1)
+        if c.shape[0] != N:
+            raise Pose6dError(f"PoseEstimator: classes must have one entry per box ({N}), got {c.shape[0]}")
+        rows = np.full(N, -1, np.int64)
+        for i, k in enumerate(c.tolist()):
+            key = k if self.class_to_obj is None else self.class_to_obj.get(k)
+            rows[i] = self._row.get(key, -1)
+        return rows
+
+    def _stage_frames(self, rgb, depth):
+        dev = self.device
+        rgb = rgb if isinstance(rgb, torch.Tensor) else torch.from_numpy(np.require(rgb, requirements="CW"))
+        if rgb.dim() == 3:
+            rgb = rgb[None]
+        if rgb.dtype != torch.uint8 or rgb.dim() != 4 or rgb.shape[-1] != 3:
+            raise Pose6dError(f"PoseEstimator: rgb must be (F, H, W, 3) uint8, got {tuple(rgb.shape)} {rgb.dtype}")
+        F, H, W, _ = rgb.shape
+        if F > self.max_frames:
+            raise Pose6dError(f"PoseEstimator: {F} frames given, max_frames = {self.max_frames}")
+        if self._frames is None or self._frames.shape[1:3] != (H, W):
+            # a new frame size: new static buffers, so graphs captured on the old ones go
+            self._frames = torch.zeros(self.max_frames, H, W, 3, dtype=torch.uint8, device=dev)
+            self._depth = torch.zeros(self.max_frames, H, W, dtype=torch.int16, device=dev).view(torch.uint16)
+            for bk in self._buckets.values():
+                bk.graph = None
+        self._frames[:F].copy_(rgb, non_blocking=True)
+        if depth is not None:
+            depth = depth if isinstance(depth, torch.Tensor) else torch.from_numpy(np.require(depth, requirements="CW"))
+            if depth.dim() == 2:
+                depth = depth[None]
+            if tuple(depth.shape) != (F, H, W):
+                raise Pose6dError(f"PoseEstimator: depth must be (F, H, W) = {(F, H, W)}, got {tuple(depth.shape)}")
+            if depth.dtype != torch.uint16:
+                depth = depth.to(torch.int32).clamp_(0, 65535).to(torch.uint16)
+            self._depth[:F].copy_(depth, non_blocking=True)
+        return F
+
+    def _run(self, bk, has_depth):
+        """crop -> eval forward -> projection on bucket bk's buffers (the graph's body)."""
+        crops = self.cropper(self._frames, self._depth if has_depth else None, bk.boxes, bk.frame_of, self._K,
+                             out=bk.crops)
+        quat, trans = self.model(*self._inputs(crops))
+        res = bk.res
+        res._quat.copy_(quat)
+        res._trans.copy_(trans.reshape(bk.B, 3))
+        pose_project(res._quat, res._trans, self._K, bk.obj, self.corners,
+                     boxes=bk.boxes if self.corrects_translation else None, frame_of=bk.frame_of,
+                     axis_scale=self.axis_scale, out=(res._trans_cam, res._points, res._pixels, res._valid))
+
+    def __call__(self, rgb, depth, boxes, classes, frame_of=None):
+        if self.model.training:
+            raise Pose6dError("PoseEstimator: the model is in training mode; call model.eval() first")
+        bx = _host_boxes(boxes.cpu() if isinstance(boxes, torch.Tensor) else boxes)
+        N = bx.shape[0]
+        if N > self.max_detections:
+            raise Pose6dError(f"PoseEstimator: {N} detections, max_detections = {self.max_detections}")
+        if N == 0:
+            return PoseResult(torch.zeros(PoseResult.nbytes(1), dtype=torch.uint8, device=self.device), 1, 0)
+        B = next(b for b in BUCKETS if b >= N)
+        rgb_frames = rgb.shape[0] if rgb.ndim == 4 else 1
+        fo = np.zeros(N, np.int64) if frame_of is None else _host_frame_of(frame_of, N, rgb_frames)
+        rows = self._objs(classes, N)
+        F = self._stage_frames(rgb, depth)
+        assert F == rgb_frames
+        has_depth = depth is not None
+        bk = self._buckets.get((B, has_depth))
+        if bk is None:
+            bk = self._buckets[(B, has_depth)] = _Bucket(B, self.device, self.cropper)
+        # pad by repeating detection 0; one small host -> device copy per table
+        pad = lambda a: np.concatenate([a, np.repeat(a[:1], B - N, axis=0)]) if B > N else a
+        bk.boxes.copy_(torch.from_numpy(pad(bx).astype(np.int32)), non_blocking=True)
+        bk.frame_of.copy_(torch.from_numpy(pad(fo).astype(np.int32)), non_blocking=True)
+        bk.obj.copy_(torch.from_numpy(pad(rows)), non_blocking=True)
+        own, self.model._p6_engines = self.model._p6_engines, bk.engines
+        try:
+            with torch.no_grad():
+                if not self.graph:
+                    self._run(bk, has_depth)
+                else:
+                    if bk.graph is None:
+                        self._capture(bk, has_depth)
+                    bk.graph.replay()
+        finally:
+            self.model._p6_engines = own
+        return PoseResult(bk.out, B, N)
+
+    def _capture(self, bk, has_depth):
+        s = torch.cuda.Stream(device=self.device)
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            self._run(bk, has_depth)   # warm-up: builds this bucket's engines, packs their weights
+        torch.cuda.current_stream().wait_stream(s)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            self._run(bk, has_depth)
+        bk.graph = g

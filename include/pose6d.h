@@ -267,6 +267,71 @@ int pose6d_crop_rgbd_train_indexed(const uint8_t *rgb_store, int32_t bgr, const 
                                    float *K_out, float *quat_out, float *trans_out, int64_t *obj_out,
                                    float *params_out, int32_t *status, void *stream);
 
+/* ----------------------------------------------------------------------
+ * Detection crops -- the per-detection body of the reference's inference scripts up
+ * to the model call (scripts/inference/inference_rgbd_geometric.py:110-182; the other
+ * three scripts use subsets of it): one launch turns N detector boxes over F frames
+ * into the model inputs.
+ * frames [F][H][W][3] uint8 (bgr as pose6d_crop_rgbd), depth [F][H][W] uint16 mm or
+ * NULL (= zeros); frame_of [N] int32 device or NULL (every detection on frame 0);
+ * boxes_xyxy [N][4] int32 (x1, y1, x2, y2) DEVICE memory read at kernel time (a
+ * captured launch follows later writes); K DOUBLE, [9] or, with K_per_frame != 0,
+ * [F][9] (the reference's DEFAULT_K is float64 and the scripts' arithmetic on it runs
+ * in Python double).  N <= 65535.
+ * Geometry (:118-135): pose6d_crop_rgbd's square crop on (x1, y1, x2 - x1, y2 - y1).
+ * RGB: pose6d_crop_rgbd's 8U resize, ToTensor, Normalize, unchanged.  Depth: resized
+ * as FLOAT32 (:142: cv2.resize(crop_depth.astype(np.float32))): the 16U path's
+ * coefficients and mul + add without its rounding to whole millimetres and saturation
+ * (exact 2x: (a + b + c + d) * 0.25f), then / 1000.f and the same normalisation on
+ * the unrounded value -- depth outputs differ from pose6d_crop_rgbd's by up to half a
+ * millimetre.
+ * Outputs (each may be NULL), fp32: rgb_out [N][3][S][S], depth_out [N][1][S][S],
+ * depth_raw_out [N][S][S];
+ * center_crop_out [N][2] = f32((c_box + pad - (crop origin + pad)) * scale) clipped
+ * to [0, S - 1], scale = S / crop side, all in double before the one cast (:145-153);
+ * K_crop_out [N][9] (:156-167), double then one cast: k_mode 0 = the script's
+ * cx_crop = (cx + pad_l - crop_x1) * scale with the UNPADDED origin crop_x1; k_mode 1
+ * = the dataset's (cx - crop_x1) * scale (dataset_rgbd.py:159-169, where the origin
+ * has the pad added back).  The script's value is pad_l * scale (pad_t * scale)
+ * larger on a box padded at the left (top); the models were trained on the
+ * dataset's;
+ * center_img_out [N][2] = f32 of the box centre, K_img_out [N][9] = f32(K)
+ * (inference_rgb_geometric.py:105-106).
+ * A frame_of[b] outside [0, F) reads nothing: detection b's outputs are zeros and
+ * *status (one device int32, may be NULL; the caller zeroes it) is raised to b + 1 by
+ * atomicMax.  N == 0 launches nothing.
+ * ---------------------------------------------------------------------- */
+int pose6d_crop_detections(const uint8_t *frames, int32_t bgr, const uint16_t *depth, int32_t F, int32_t H, int32_t W,
+                           const int32_t *frame_of, const int32_t *boxes_xyxy, int32_t N, const double *K,
+                           int32_t K_per_frame, int32_t S, const float *mean_std, int32_t k_mode, float *rgb_out,
+                           float *depth_out, float *depth_raw_out, float *center_crop_out, float *K_crop_out,
+                           float *center_img_out, float *K_img_out, int32_t *status, void *stream);
+
+/* ----------------------------------------------------------------------
+ * What the inference scripts do after the model call, for N detections in one launch,
+ * in fp64 as the reference's host numpy: translation correction, then the projection
+ * of 12 points per detection -- the object's 8 box corners, the origin and the three
+ * axis tips at axis_scale (utils/visualization.py:8-32, :63-66).
+ * quat [N][4] fp32 (x, y, z, w: scipy's order), trans [N][3] fp32; K double [9] or
+ * [F][9] with frame_of [N] (K_per_frame as above; F >= 1); obj [N] int64 rows into
+ * corners [n_obj][8][3] double.
+ * Translation: boxes_xyxy != NULL (the RGB and RGBD scripts, inference_rgb.py:99-104):
+ * z = (double)trans[2], x = (c_x_box - cx) * z / fx, y alike; NULL: (double)trans.
+ * Rotation: scipy's Rotation.from_quat(q).as_matrix() -- cast to double, divide by the
+ * norm, the unit-quaternion matrix.  Projection: p = R c + t, z = max(p.z, 0.001),
+ * u = p.x * K00 / z + K02, v alike.
+ * Outputs (each may be NULL): trans_out [N][3] double, pts_out [N][12][2] double,
+ * pix_out [N][12][2] int64 = the points truncated toward zero (numpy's astype(int));
+ * a NaN, an infinity or a value outside int64 gives INT64_MIN, as numpy does on
+ * x86-64.  valid_out [N] uint8: 0, with that detection's rows zeroed, for an obj
+ * outside [0, n_obj) (the scripts skip an object without a mesh), a quaternion whose
+ * norm is zero or NaN (scipy raises on zero) or a frame_of outside [0, F).
+ * ---------------------------------------------------------------------- */
+int pose6d_pose_project(const float *quat, const float *trans, const int32_t *boxes_xyxy, const double *K,
+                        int32_t K_per_frame, const int32_t *frame_of, int32_t F, const int64_t *obj,
+                        const double *corners, int64_t n_obj, double axis_scale, int32_t N, double *trans_out,
+                        double *pts_out, int64_t *pix_out, uint8_t *valid_out, void *stream);
+
 /* ------------------------------------------------------------------------
  * ResNet50 trunk — replaces torchvision.models.resnet50 children[:-1] as
  * wrapped by every model (pose_net_rgb.py:18-20, pose_net_rgb_geometric.py:18-20,
