@@ -18,6 +18,8 @@
 //   add_reduce_kernel  grid B: fixed-order fp64 means (deterministic), 0.1d test.
 //   val_append_kernel  one workgroup: the batch's per-sample results become rows of a
 //                      device-resident epoch table (the validation pass, pose6d.validate).
+//   add_head_loss_kernel / add_head_loss_finish_kernel  ADDLoss.forward and its gradient as a
+//                      term of the whole-step trainers' criterion (pose6d_add_head_loss, below).
 //
 // Bit-exactness contract (pinned by tests/golden/add_loss.npz):
 // this file is built with -ffp-contract=off; the only fused ops are the explicit
@@ -460,6 +462,239 @@ __global__ __launch_bounds__(kThreads) void add_loss_bwd_kernel(
   for (int i = 0; i < 4; ++i) grad_rot[4 * b + i] = (float)gq[i];
 }
 
+// ---------------------------------------------------------------- ADD loss in the training step
+// pose6d_add_head_loss: ADDLoss.forward (add_loss.py:101-150) and its gradient on the head's
+// unnormalised quaternion, ADDED to what the step's head + PoseLoss launch wrote.  One
+// workgroup per sample: q = normalize(raw) (rownorm_fwd_kernel's arithmetic), Q and G as
+// add_points_kernel computes them, the ADD-S nearest-point search only for a symmetric
+// sample, fp64 block sums of d, g = (Q - G*) / d and g P^T (add_loss_bwd_kernel's), then the
+// chain rule through _quat_to_mat and the normalise.  Every workgroup counts the batch's
+// known samples itself, so the gradient waits for no other workgroup; the one cross-sample
+// sum (the loss) is add_head_loss_finish_kernel's, a launch of its own.
+//
+// The search is the in-order sweep of add_points_kernel<.., false> (the same first-index
+// rule, so the same index), pruned by a bound: any candidate gives an upper bound S on the
+// smallest squared distance, and only candidates with s <= S (1 + 2^-19) can be the minimum
+// or share its root (see add_points_kernel), so a trip of four ground-truth points in which
+// no lane of the wave has such a candidate is skipped.  The bound starts from the point's
+// own ground-truth point and, with a neighbour table, a two-hop walk on it; it only decides
+// which trips are skipped, never an index, so the result does not depend on the table.
+constexpr float kNormEps = 1e-12f;   // F.normalize default eps (pose_head.hip)
+constexpr float kGeoEps = 1e-8f;     // pose_net_rgb_geometric.py:75
+
+__global__ __launch_bounds__(kThreads) void add_head_loss_kernel(
+    const float* __restrict__ raw, int norm_mode, const float* __restrict__ trans, const float* __restrict__ gt_rot,
+    const float* __restrict__ gt_trans, const int64_t* __restrict__ obj_ids, int B, const float* __restrict__ points,
+    const int32_t* __restrict__ off, const int32_t* __restrict__ npts, const uint8_t* __restrict__ sym, int n_slots,
+    int max_npts, const uint16_t* __restrict__ nbr, int K, float add_weight, int trans_mode,
+    const float* __restrict__ bbox, const float* __restrict__ cam_K, int Kb, float* __restrict__ grad_raw,
+    float* __restrict__ grad_trans, double* __restrict__ per, int32_t* __restrict__ nearest) {
+  __shared__ float4 gs[kTile];
+  __shared__ double red[13][kThreads / 64];
+  __shared__ int cnt_s[kThreads / 64];
+  const int b = blockIdx.x, tid = threadIdx.x, w = tid >> 6;
+  const int64_t oid = obj_ids[b];
+  const int n = (oid >= 0 && oid < n_slots) ? npts[oid] : 0;
+  if (n <= 0) {
+    if (tid == 0) per[b] = 0.0;
+    return;
+  }
+  // count of samples that enter the loss (known objects with points)
+  int c = 0;
+  for (int i = tid; i < B; i += kThreads) {
+    const int64_t o = obj_ids[i];
+    c += (o >= 0 && o < n_slots && npts[o] > 0) ? 1 : 0;
+  }
+  c = p6::wave_sum(c);
+  if ((tid & 63) == 0) cnt_s[w] = c;
+
+  // q = normalize(raw): rownorm_fwd_kernel's arithmetic (the bits of the step's `rot`)
+  const float* xr = raw + 4 * b;
+  const float nrm = sqrtf(fmaf(xr[3], xr[3], fmaf(xr[2], xr[2], fmaf(xr[1], xr[1], fmaf(xr[0], xr[0], 0.f)))));
+  const float den = norm_mode == 0 ? fmaxf(nrm, kNormEps) : nrm + kGeoEps;
+  const float q[4] = {xr[0] / den, xr[1] / den, xr[2] / den, xr[3] / den};
+  const Mat3 Rp = quat_to_mat(q);
+  const Mat3 Rg = quat_to_mat(gt_rot + 4 * b);
+  const float* tp = trans + 3 * b;
+  const float* tg = gt_trans + 3 * b;
+  const float* P = points + 3 * (int64_t)off[oid];
+  const bool is_sym = sym[oid] != 0;
+  const bool in_lds = n <= kTile;   // the whole ground truth is one tile, staged once
+  const uint16_t* nb = nbr ? nbr + (int64_t)off[oid] * K : nullptr;
+  auto cand = [&](int j) { return in_lds ? gs[j] : xform(P + 3 * j, Rg, tg, n); };
+  if (is_sym && in_lds) {
+    for (int jj = tid; jj < n; jj += kThreads) gs[jj] = xform(P + 3 * jj, Rg, tg, n);
+    __syncthreads();
+  }
+
+  double acc[13];   // sum d, gt[3], gR[3][3] (row = output coordinate, col = point coordinate)
+#pragma unroll
+  for (int i = 0; i < 13; ++i) acc[i] = 0.0;
+  for (int k0 = 0; k0 < n; k0 += kThreads) {
+    const int k = k0 + tid;
+    const bool act = k < n;
+    float4 qp = {0.f, 0.f, 0.f, 0.f};
+    if (act) qp = xform(P + 3 * k, Rp, tp, n);
+    int j = k;
+    if (is_sym) {
+      // idle lanes: nothing beats -inf, nothing is <= a -inf bound
+      float best = act ? __builtin_inff() : -__builtin_inff(), thr = best;
+      int bi = 0;
+      if (act) {
+        float s0 = sqdist(qp.x, qp.y, qp.z, cand(k));
+        if (!(s0 == s0)) s0 = __builtin_inff();   // NaN never becomes a minimum
+        if (nb) {
+          int cur = k, sj = k;
+          for (int h = 0; h < kAddHops; ++h) {
+            const uint16_t* row = nb + (int64_t)cur * K;
+            for (int t = 0; t < K; t += 8) {
+              const uint4 wd = *reinterpret_cast<const uint4*>(row + t);   // 8 indices (K % 8 == 0, 16-B rows)
+              const uint32_t ww[4] = {wd.x, wd.y, wd.z, wd.w};
+#pragma unroll
+              for (int e = 0; e < 8; ++e) {
+                const int ji = min((int)((ww[e >> 1] >> (16 * (e & 1))) & 0xffffu), n - 1);   // clamped: a genuine candidate
+                const float s = sqdist(qp.x, qp.y, qp.z, cand(ji));
+                if (s < s0) { s0 = s; sj = ji; }
+              }
+            }
+            if (sj == cur) break;   // nothing nearer around cur
+            cur = sj;
+          }
+        }
+        thr = s0 + s0 * 0x1p-19f;
+      }
+      // in order: a new squared minimum keeps the old, earlier index iff the roots are equal
+      auto update = [&](float s, int jn) {
+        if (s < best) {
+          const float gap = best - s;   // exact when the two are close (Sterbenz)
+          if (!(gap <= best * 0x1p-20f) || sqrtf(s) != sqrtf(best)) bi = jn;
+          best = s;
+          thr = fminf(thr, s + s * 0x1p-19f);
+        }
+      };
+      for (int j0 = 0; j0 < n; j0 += kTile) {
+        const int jn = min(kTile, n - j0);
+        if (!in_lds) {
+          __syncthreads();
+          for (int jj = tid; jj < jn; jj += kThreads) gs[jj] = xform(P + 3 * (j0 + jj), Rg, tg, n);
+          __syncthreads();
+        }
+        int jj = 0;
+        for (; jj + 4 <= jn; jj += 4) {
+          float s[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) s[u] = sqdist(qp.x, qp.y, qp.z, gs[jj + u]);
+          const float m = __builtin_fminf(__builtin_fminf(s[0], s[1]), __builtin_fminf(s[2], s[3]));
+          if (__ballot(m <= thr) != 0) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) update(s[u], j0 + jj + u);
+          }
+        }
+        for (; jj < jn; ++jj) update(sqdist(qp.x, qp.y, qp.z, gs[jj]), j0 + jj);
+      }
+      j = bi;
+    }
+    if (!act) continue;
+    const float4 g = is_sym ? cand(j) : xform(P + 3 * k, Rg, tg, n);
+    if (nearest) nearest[(int64_t)b * max_npts + k] = j;
+    const float dx = qp.x - g.x, dy = qp.y - g.y, dz = qp.z - g.z;
+    const float d = sqrtf(fmaf(dz, dz, fmaf(dy, dy, dx * dx)));
+    if (d == 0.f) continue;   // torch's norm backward: 0 at distance 0
+    acc[0] += (double)d;
+    const double gx = dx / d, gy = dy / d, gz = dz / d;
+    const double p0 = P[3 * k], p1 = P[3 * k + 1], p2 = P[3 * k + 2];
+    acc[1] += gx; acc[2] += gy; acc[3] += gz;
+    acc[4] += gx * p0; acc[5] += gx * p1; acc[6] += gx * p2;
+    acc[7] += gy * p0; acc[8] += gy * p1; acc[9] += gy * p2;
+    acc[10] += gz * p0; acc[11] += gz * p1; acc[12] += gz * p2;
+  }
+#pragma unroll
+  for (int i = 0; i < 13; ++i) {
+    const double v = p6::wave_sum(acc[i]);
+    if ((tid & 63) == 0) red[i][w] = v;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  int cnt = 0;
+  for (int i = 0; i < kThreads / 64; ++i) cnt += cnt_s[i];
+  double t[13];
+#pragma unroll
+  for (int i = 0; i < 13; ++i) {
+    double v = 0.0;
+    for (int i2 = 0; i2 < kThreads / 64; ++i2) v += red[i][i2];
+    t[i] = v;
+  }
+  per[b] = t[0] / (double)n;
+  const double scale = (double)add_weight / ((double)cnt * (double)n);
+  for (int i = 1; i < 13; ++i) t[i] *= scale;
+  if (trans_mode == 0) {
+    for (int i = 0; i < 3; ++i) grad_trans[3 * b + i] += (float)t[1 + i];
+  } else if (trans_mode == 2) {
+    // back through the pinhole of the predicted depth (pinhole_z_bwd_kernel's formula)
+    const float* kk = Kb ? cam_K + 9 * (int64_t)b : cam_K;
+    const double fx = kk[0], cx = kk[2], fy = kk[4], cy = kk[5];
+    grad_trans[b] += (float)(t[1] * ((double)bbox[2 * b] - cx) / fx + t[2] * ((double)bbox[2 * b + 1] - cy) / fy + t[3]);
+  }
+  const double* G = t + 4;   // dL/dR[a][c], row-major r0..r8
+  const double x = q[0], y = q[1], z = q[2], qw = q[3];
+  // d r / d(x, y, z, w) of add_loss.py:203-215
+  const double drx[9] = {0, 2 * y, 2 * z, 2 * y, -4 * x, -2 * qw, 2 * z, 2 * qw, -4 * x};
+  const double dry[9] = {-4 * y, 2 * x, 2 * qw, 2 * x, 0, 2 * z, -2 * qw, 2 * z, -4 * y};
+  const double drz[9] = {-4 * z, -2 * qw, 2 * x, 2 * qw, -4 * z, 2 * y, 2 * x, 2 * y, 0};
+  const double drw[9] = {0, -2 * z, 2 * y, 2 * z, 0, -2 * x, -2 * y, 2 * x, 0};
+  double gq[4] = {0, 0, 0, 0};
+  for (int i = 0; i < 9; ++i) {
+    gq[0] += G[i] * drx[i];
+    gq[1] += G[i] * dry[i];
+    gq[2] += G[i] * drz[i];
+    gq[3] += G[i] * drw[i];
+  }
+  // back through the normalise (rownorm_bwd_row's cases, in fp64)
+  const double xd[4] = {xr[0], xr[1], xr[2], xr[3]};
+  const double nd = sqrt(xd[0] * xd[0] + xd[1] * xd[1] + xd[2] * xd[2] + xd[3] * xd[3]);
+  const double xg = xd[0] * gq[0] + xd[1] * gq[1] + xd[2] * gq[2] + xd[3] * gq[3];
+  double dxr[4];
+  if (norm_mode == 0) {
+    if (nd > (double)kNormEps) {
+      for (int i = 0; i < 4; ++i) dxr[i] = gq[i] / nd - xd[i] * xg / (nd * nd * nd);
+    } else {
+      for (int i = 0; i < 4; ++i) dxr[i] = gq[i] / (double)kNormEps;   // clamp_min: no grad to the norm
+    }
+  } else {
+    const double dd = nd + (double)kGeoEps;
+    const double cc = nd > 0.0 ? xg / (dd * dd * nd) : 0.0;             // norm grad is 0 at 0
+    for (int i = 0; i < 4; ++i) dxr[i] = gq[i] / dd - xd[i] * cc;
+  }
+  for (int i = 0; i < 4; ++i) grad_raw[4 * b + i] += (float)dxr[i];
+}
+
+// loss[0] += add_weight * (sum of per[] over the known samples) / count: ONE workgroup, per[]
+// summed in a fixed order (per[b] is 0 for an unknown sample), so the bits repeat; nothing
+// is added when no sample is known.
+__global__ __launch_bounds__(kThreads) void add_head_loss_finish_kernel(
+    const int64_t* __restrict__ obj_ids, int B, const int32_t* __restrict__ npts, int n_slots,
+    const double* __restrict__ per, float add_weight, float* __restrict__ loss) {
+  __shared__ double red[kThreads / 64];
+  __shared__ int cnt_s[kThreads / 64];
+  const int tid = threadIdx.x;
+  int c = 0;
+  double s = 0.0;
+  for (int i = tid; i < B; i += kThreads) {
+    const int64_t o = obj_ids[i];
+    c += (o >= 0 && o < n_slots && npts[o] > 0) ? 1 : 0;
+    s += per[i];
+  }
+  c = p6::wave_sum(c);
+  s = p6::wave_sum(s);
+  if ((tid & 63) == 0) { cnt_s[tid >> 6] = c; red[tid >> 6] = s; }
+  __syncthreads();
+  if (tid != 0) return;
+  int cnt = 0;
+  double tot = 0.0;
+  for (int i = 0; i < kThreads / 64; ++i) { cnt += cnt_s[i]; tot += red[i]; }
+  if (cnt > 0) loss[0] += add_weight * (float)(tot / (double)cnt);
+}
+
 }  // namespace
 
 extern "C" int pose6d_add_neighbors(const float* points, const int32_t* off, const int32_t* npts, int32_t n_slots,
@@ -549,6 +784,38 @@ extern "C" int pose6d_add_loss_bwd(const float* pred_rot, const float* pred_tran
   add_loss_bwd_kernel<<<(unsigned)B, kThreads, 0, p6::stream_of(stream)>>>(
       pred_rot, pred_trans, gt_rot, gt_trans, obj_ids, (int)B, points, off, npts, sym, n_slots, max_npts, argmin,
       dloss, grad_rot, grad_trans);
+  P6_LAUNCH_CHECK();
+  return POSE6D_OK;
+}
+
+extern "C" int pose6d_add_head_loss(const float* raw, int32_t norm_mode, const float* trans, const float* gt_rot,
+                                    const float* gt_trans, const int64_t* obj_ids, int64_t B, const float* points,
+                                    const int32_t* off, const int32_t* npts, const uint8_t* sym, int32_t n_slots,
+                                    int32_t max_npts, const uint16_t* nbr, int32_t K, float add_weight,
+                                    int32_t trans_mode, const float* bbox_center, const float* cam_K,
+                                    int32_t K_batched, float* loss, float* grad_raw, float* grad_trans, double* per,
+                                    int32_t* nearest, void* stream) {
+  P6_CHECK_ARG(B > 0 && B <= 65535, "pose6d_add_head_loss: batch %lld out of range", (long long)B);
+  P6_CHECK_ARG(norm_mode == 0 || norm_mode == 1, "pose6d_add_head_loss: bad norm_mode %d", (int)norm_mode);
+  P6_CHECK_ARG(trans_mode >= 0 && trans_mode <= 2, "pose6d_add_head_loss: bad trans_mode %d", (int)trans_mode);
+  P6_CHECK_ARG(n_slots >= 0 && max_npts >= 0, "pose6d_add_head_loss: bad table sizes");
+  P6_CHECK_ARG(!nbr || ((K == 8 || K == 16 || K == 32) && max_npts <= 65536 && ((uintptr_t)nbr & 15) == 0),
+               "pose6d_add_head_loss: the neighbour table needs K in {8, 16, 32}, <= 65536 points per mesh and "
+               "16-byte alignment");
+  P6_CHECK_ARG(raw && trans && gt_rot && gt_trans && obj_ids && loss && grad_raw && per,
+               "pose6d_add_head_loss: null argument");
+  P6_CHECK_ARG(n_slots == 0 || (points && off && npts && sym), "pose6d_add_head_loss: null mesh table");
+  P6_CHECK_ARG(trans_mode == 1 || grad_trans, "pose6d_add_head_loss: trans_mode %d needs grad_trans",
+               (int)trans_mode);
+  P6_CHECK_ARG(trans_mode != 2 || (bbox_center && cam_K),
+               "pose6d_add_head_loss: trans_mode 2 needs bbox_center and the intrinsics");
+  hipStream_t s = p6::stream_of(stream);
+  add_head_loss_kernel<<<(unsigned)B, kThreads, 0, s>>>(raw, norm_mode, trans, gt_rot, gt_trans, obj_ids, (int)B,
+                                                        points, off, npts, sym, n_slots, max_npts, nbr, K, add_weight,
+                                                        trans_mode, bbox_center, cam_K, K_batched, grad_raw,
+                                                        grad_trans, per, nearest);
+  P6_LAUNCH_CHECK();
+  add_head_loss_finish_kernel<<<1, kThreads, 0, s>>>(obj_ids, (int)B, npts, n_slots, per, add_weight, loss);
   P6_LAUNCH_CHECK();
   return POSE6D_OK;
 }

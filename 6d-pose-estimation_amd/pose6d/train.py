@@ -89,14 +89,29 @@ class FlatArena:
 
 
 class RGBDGeometricTrainer:
-    """Fused, graph-captured training step for PoseNetRGBDGeometric."""
+    """Fused, graph-captured training step for PoseNetRGBDGeometric.
+
+    add_loss (a models.add_loss.ADDLoss; every trainer of this module takes it) adds
+    add_weight * ADDLoss.train_loss (add_loss.py:101-154: the mean ADD, ADD-S for the symmetric
+    objects, over the batch's known objects) to the criterion: one more launch
+    (pose6d_add_head_loss) after the head + PoseLoss launch, inside the captured step.
+    rot_weight / trans_weight stay PoseLoss's weights; both 0 = the ADD loss alone.  The
+    step's object ids are read at run time from self.obj_ids (int64 [B]; it starts at -1 =
+    unknown object = no ADD term): write it in place (obj_ids.copy_(ids), step(data,
+    obj_ids=ids), or as element 5 of the tuple given to EpochFeeder.into).  The data tuples
+    and checkpoints do not change.  The mesh table is bound at construction: step() raises if
+    ADDLoss.points / diameters changed after capture() (a graph bakes the pointers in);
+    capture() again binds the new table.  Under a process group each rank's ADD term is the
+    mean over its own known samples (torch DDP's result with the reference's loss).
+    add_loss=None: PoseLoss alone, the launches and bits of a trainer built without it."""
 
     # POSE6D_HEAD_WGRAD_SIDE applies (RGBTrainer's step is one chain whatever it says)
     _head_wgrad_side = True
 
     def __init__(self, model, batch, dtype=torch.bfloat16, lr=1e-4, weight_decay=1e-4, max_norm=1.0,
                  betas=(0.9, 0.999), eps=1e-8, rot_weight=1.0, trans_weight=10.0, process_group=None,
-                 bucket_mb=25.0, tail_mb=2.0, force_buckets=False, pack_in_adamw=True):
+                 bucket_mb=25.0, tail_mb=2.0, force_buckets=False, pack_in_adamw=True, add_loss=None,
+                 add_weight=1.0):
         self.model = model
         self.B = batch
         dev = next(model.parameters()).device
@@ -150,6 +165,18 @@ class RGBDGeometricTrainer:
         self.pg = process_group
         self.graphs = None
         self._buckets(bucket_mb, tail_mb)
+        # the ADD / ADD-S term of the criterion (models.add_loss.ADDLoss, or None: PoseLoss alone,
+        # the launches and bits of a trainer built without it)
+        self.add_loss = add_loss
+        if add_loss is not None:
+            self.add_weight = float(add_weight)
+            # the step's object ids: written by the caller (tr.obj_ids.copy_(ids), step(data,
+            # obj_ids=ids), or as element 5 of EpochFeeder.into(...)'s tuple) and read by the
+            # launch at run time; -1 = unknown object = no ADD term for that sample
+            self.obj_ids = torch.full((batch,), -1, device=dev, dtype=torch.int64)
+            self.add_per = torch.zeros(batch, device=dev, dtype=torch.float64)
+            self._add_table = None
+            self._bind_add_table()
 
     def _build_trunks(self, model):
         """The trunk engines, in the order their backwards run (the arena's order after
@@ -218,6 +245,32 @@ class RGBDGeometricTrainer:
         ends[-1] = (ends[-1][0], self.arena.numel)   # the last bucket covers the alignment tail
         self.bucket_ends = [(self.arena.params[i], e) for i, e in ends]
 
+    # ------------------------------------------------------------- the ADD criterion
+    def _bind_add_table(self, capturing=False):
+        """The mesh table the ADD launch reads (ADDLoss's packed device copy), bound at
+        construction.  A captured graph bakes its pointers in, so a table that changed after
+        capture() (ADDLoss.points / diameters edited: a host-only key comparison) makes step()
+        raise; before a capture, and in capture() itself, the new table is bound."""
+        if self.add_loss is None:
+            return
+        T = self.add_loss._mesh_table(self.dev)
+        if T is self._add_table:
+            return
+        if self.graphs is not None and not capturing:
+            raise Pose6dError("the ADDLoss mesh table changed after capture(): the captured step reads the old "
+                              "table; build the trainer's graph again (capture) after editing ADDLoss.points")
+        self._add_table = T      # (held: the graph's pointers stay alive)
+
+    def _add_head_loss(self, raw, trans, gt_rot, gt_trans, norm_mode, trans_mode, grad_trans=None, bbox=None,
+                       K=None):
+        """add_weight * ADDLoss.train_loss and its gradient ADDED to self.loss / self.draw /
+        grad_trans, which the head + PoseLoss launch has just written (pose6d_add_head_loss)."""
+        T = self._add_table
+        call("add_head_loss", raw, norm_mode, trans, gt_rot, gt_trans, self.obj_ids, self.B, T.points, T.off, T.npts,
+             T.sym, T.n_slots, T.max_npts, T.nbr, T.K, self.add_weight, trans_mode, bbox, K,
+             0 if K is None else (1 if K.dim() == 3 else 0), self.loss, self.draw, grad_trans, self.add_per, None,
+             stream())
+
     # ------------------------------------------------------------- the step
     def _forward_loss(self, rgb, depth_raw, bbox, K, gt_rot, gt_trans):
         st = stream()
@@ -228,6 +281,8 @@ class RGBDGeometricTrainer:
         call("geo_head_loss", raw, depth_raw, depth_raw.shape[1], depth_raw.shape[2], bbox, K,
              1 if K.dim() == 3 else 0, gt_rot, gt_trans, self.B, self.wr, self.wt, 0, self.rot, self.trans, self.loss,
              self.draw, self.dtrans, st)
+        if self.add_loss is not None:   # the pinhole translation is not learned: no gradient to it
+            self._add_head_loss(raw, self.trans, gt_rot, gt_trans, 0, 1)
         return raw
 
     def _head_backward(self, wgrad_stream=None):
@@ -290,6 +345,7 @@ class RGBDGeometricTrainer:
     def step_eager(self, data):
         """One training step without graphs (reference order of operations)."""
         self._sync_if_stale()
+        self._bind_add_table()
         if not self._ddp:
             return self.step_body(data, branch=True)
         self._pack()
@@ -351,6 +407,7 @@ class RGBDGeometricTrainer:
         backward as graph segments cut where a gradient bucket completes, and the
         optimizer as a graph of its own (the all-reduces run between replays)."""
         self._sync_if_stale()
+        self._bind_add_table(capturing=True)
         s = torch.cuda.Stream(device=self.dev)
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -417,8 +474,13 @@ class RGBDGeometricTrainer:
         self._red = BucketReducer(self.arena.grad, self.bucket_ends, self.pg, self._comm_stream())
         return segs + [(opt, None)]
 
-    def step(self, data=None):
+    def step(self, data=None, obj_ids=None):
+        """One training step: a replay of the captured graph(s), or step_eager(data) before
+        capture().  obj_ids (with an ADDLoss criterion): copied into self.obj_ids first."""
         self._sync_if_stale()
+        if obj_ids is not None:
+            self.obj_ids.copy_(obj_ids)
+        self._bind_add_table()
         if self.graphs is None:
             return self.step_eager(data)
         if not self._ddp:
@@ -539,6 +601,8 @@ class RGBTrainer(RGBDGeometricTrainer):
         call("quat_head_loss", raw, trans, gt_rot, gt_trans, self.B, self.wr, self.wt, 0, 0, self.rot, self.loss,
              self.draw, self.dtrans, st)
         self.trans = trans
+        if self.add_loss is not None:
+            self._add_head_loss(raw, trans, gt_rot, gt_trans, 0, 0, grad_trans=self.dtrans)
         return raw
 
     def _head_backward(self, wgrad_stream=None):
@@ -616,6 +680,8 @@ class RGBGeometricTrainer(RGBDGeometricTrainer):
         # arithmetic of the rownorm_* / pinhole_z_* / pose_loss_* entry points)
         call("zgeo_head_loss", raw, z, bbox, K, 1 if K.dim() == 3 else 0, gt_rot, gt_trans, self.B, self.wr, self.wt,
              0, self.rot, self.trans, self.loss, self.draw, self.dz, st)
+        if self.add_loss is not None:   # the translation gradient folds through the pinhole into dz
+            self._add_head_loss(raw, self.trans, gt_rot, gt_trans, 1, 2, grad_trans=self.dz, bbox=bbox, K=K)
         return raw
 
     def _head_backward(self, wgrad_stream=None):
@@ -694,6 +760,8 @@ class RGBDTrainer(RGBGeometricTrainer):
         call("quat_head_loss", raw, trans, gt_rot, gt_trans, self.B, self.wr, self.wt, 0, 0, self.rot, self.loss,
              self.draw, self.dtrans, st)
         self.trans = trans
+        if self.add_loss is not None:
+            self._add_head_loss(raw, trans, gt_rot, gt_trans, 0, 0, grad_trans=self.dtrans)
         return raw
 
     def _head_backward(self, wgrad_stream=None):

@@ -110,6 +110,47 @@ int pose6d_add_loss_bwd(const float *pred_rot, const float *pred_trans, const fl
                         int32_t max_npts, const int32_t *argmin, const float *dloss, float *grad_rot,
                         float *grad_trans, void *stream);
 
+/* ADDLoss.forward / train_loss (add_loss.py:101-154) as a term of the whole-step trainers'
+ * criterion: runs right after the step's head + PoseLoss launch (pose6d_geo_head_loss,
+ * pose6d_quat_head_loss, pose6d_zgeo_head_loss) on the same raw / trans and ADDS
+ * add_weight * L and its gradient to what that launch wrote.  No host synchronisation, no
+ * allocation, everything (obj_ids included) read from device memory at run time, so a
+ * replayed graph follows new obj_ids.  Two launches: one workgroup per sample, then one
+ * workgroup that sums the samples in a fixed order (bitwise repeatable).
+ *   raw [B][4]: the head's unnormalised quaternion; q = normalize(raw) with norm_mode as
+ *     pose6d_rownorm_* (0: F.normalize, 1: x / (||x|| + 1e-8)).
+ *   trans [B][3]: the step's translation (whatever trans_mode says).
+ *   obj_ids int64 [B]; points / off / npts / sym / n_slots / max_npts: the packed mesh
+ *     table of pose6d_add_eval.  nbr / K: the optional neighbour table of
+ *     pose6d_add_eval_nbr (NULL: none); it only shortens the ADD-S search, the index found
+ *     does not depend on it.
+ *   per sample b: Q = P R(q)^T + trans, G = P R(gt_rot)^T + gt_trans (torch-CPU's rounding,
+ *     as pose6d_add_eval); G*_k = G_k, or for a symmetric object the nearest G_j (first
+ *     index on ties, searched only for symmetric samples); per[b] = mean_k ||Q_k - G*_k||.
+ *   L = (1 / count) sum of per[b] over the samples whose object is known and has points
+ *     (count of them); count == 0: L = 0 and nothing is added anywhere.
+ * Accumulated:
+ *   loss[0]     += add_weight * L
+ *   grad_raw[b] += add_weight * dL/draw[b]  (through _quat_to_mat, add_loss.py:203-215, and the
+ *                  normalise; a zero distance contributes zero, as torch's norm backward)
+ *   trans_mode 0 (a learned translation head): grad_trans [B][3] += add_weight * dL/dtrans
+ *   trans_mode 1 (a translation that is not learned): grad_trans is not touched (may be NULL)
+ *   trans_mode 2 (pinhole of a learned depth z): grad_trans is grad_z [B];
+ *     grad_z[b] += add_weight * (dL/dt0 (u - cx) / fx + dL/dt1 (v - cy) / fy + dL/dt2)
+ *     (pose6d_pinhole_z_bwd's formula; needs bbox_center [B][2] and cam_K [B][3][3]
+ *     (K_batched = 1) or [3][3] (0); both are ignored in the other modes)
+ * Plain writes: per [B] doubles (0 for an unknown sample) and, if not NULL, nearest
+ * [B][max_npts] int32, the ground-truth index used per point (k itself for an asymmetric
+ * sample; rows of unknown samples and columns >= npts are not written).
+ * 0 < B <= 65535, norm_mode 0 / 1, trans_mode 0 / 1 / 2. */
+int pose6d_add_head_loss(const float *raw, int32_t norm_mode, const float *trans, const float *gt_rot,
+                         const float *gt_trans, const int64_t *obj_ids, int64_t B, const float *points,
+                         const int32_t *off, const int32_t *npts, const uint8_t *sym, int32_t n_slots,
+                         int32_t max_npts, const uint16_t *nbr, int32_t K, float add_weight,
+                         int32_t trans_mode, const float *bbox_center, const float *cam_K,
+                         int32_t K_batched, float *loss, float *grad_raw, float *grad_trans, double *per,
+                         int32_t *nearest, void *stream);
+
 /* ------------------------------------------------------------------------
  * Pose heads and loss
  * ---------------------------------------------------------------------- */
