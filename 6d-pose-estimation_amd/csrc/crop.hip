@@ -557,9 +557,11 @@ __device__ __forceinline__ void hsv2rgb(int h8, int s8, int v8, int& r, int& g, 
 
 __global__ __launch_bounds__(kAugThreads) void augment_kernel(const uint8_t* __restrict__ src, int S,
                                                               const float* __restrict__ mean_std, AugCfg cfg,
-                                                              uint64_t seed, float* __restrict__ rgb_out,
+                                                              uint64_t seed, const uint64_t* __restrict__ seed_dev,
+                                                              float* __restrict__ rgb_out,
                                                               float* __restrict__ params_out) {
   extern __shared__ __attribute__((aligned(16))) uint8_t img[];   // [S][S][3]
+  if (seed_dev) seed = *seed_dev;   // the device-seed entry point: read now, uniform over the launch
   __shared__ int red[kAugThreads / 64];
   __shared__ float prm[kAugParams];
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -716,10 +718,30 @@ extern "C" int pose6d_crop_rgbd_train(const uint8_t* rgb, int32_t bgr, const uin
   P6_LAUNCH_CHECK();
   const AugCfg cfg = aug_cfg(brightness, contrast, saturation, hue, erase_p, erase_scale_lo, erase_scale_hi,
                              erase_ratio_lo, erase_ratio_hi);
-  augment_kernel<<<B, kAugThreads, S * S * 3, s>>>(workspace, S, mean_std, cfg, seed, rgb_out, params_out);
+  augment_kernel<<<B, kAugThreads, S * S * 3, s>>>(workspace, S, mean_std, cfg, seed, nullptr, rgb_out, params_out);
   P6_LAUNCH_CHECK();
   return POSE6D_OK;
 }
+
+namespace {
+
+// The two launches of the indexed train crop: `seed` by value, or read from seed_dev at
+// kernel time when that is given.
+int launch_train_indexed(const StoreTabs& t, int bgr, int H, int W, const int64_t* sample_idx, const int32_t* bbox_aug,
+                         int B, int S, const float* mean_std, const AugCfg& cfg, uint64_t seed,
+                         const uint64_t* seed_dev, uint8_t* workspace, float* rgb_out, float* depth_out,
+                         float* depth_raw_out, float* center_out, float* K_out, const LabelOuts& lab,
+                         float* params_out, hipStream_t s) {
+  const dim3 grid(p6::ceil_div((int64_t)S * S, kThreads), B);
+  crop_rgbd_indexed_kernel<<<grid, kThreads, 0, s>>>(t, bgr, H, W, sample_idx, bbox_aug, S, nullptr, nullptr,
+                                                     depth_out, depth_raw_out, center_out, K_out, lab, workspace);
+  P6_LAUNCH_CHECK();
+  augment_kernel<<<B, kAugThreads, S * S * 3, s>>>(workspace, S, mean_std, cfg, seed, seed_dev, rgb_out, params_out);
+  P6_LAUNCH_CHECK();
+  return POSE6D_OK;
+}
+
+}  // namespace
 
 extern "C" int pose6d_crop_rgbd_train_indexed(
     const uint8_t* rgb_store, int32_t bgr, const uint16_t* depth_store, int64_t n_frames, int32_t H, int32_t W,
@@ -737,16 +759,35 @@ extern "C" int pose6d_crop_rgbd_train_indexed(
                "LDS)");
   P6_CHECK_AUG_ARGS("pose6d_crop_rgbd_train_indexed");
   if (B == 0) return POSE6D_OK;
-  hipStream_t s = p6::stream_of(stream);
   const StoreTabs t{rgb_store, depth_store, n_frames, n_samples, frame_of, bbox, K, center_tab, quat, trans, obj_id};
   const LabelOuts lab{quat_out, trans_out, obj_out, status};
-  const dim3 grid(p6::ceil_div((int64_t)S * S, kThreads), B);
-  crop_rgbd_indexed_kernel<<<grid, kThreads, 0, s>>>(t, bgr, H, W, sample_idx, bbox_aug, S, nullptr, nullptr,
-                                                     depth_out, depth_raw_out, center_out, K_out, lab, workspace);
-  P6_LAUNCH_CHECK();
   const AugCfg cfg = aug_cfg(brightness, contrast, saturation, hue, erase_p, erase_scale_lo, erase_scale_hi,
                              erase_ratio_lo, erase_ratio_hi);
-  augment_kernel<<<B, kAugThreads, S * S * 3, s>>>(workspace, S, mean_std, cfg, seed, rgb_out, params_out);
-  P6_LAUNCH_CHECK();
-  return POSE6D_OK;
+  return launch_train_indexed(t, bgr, H, W, sample_idx, bbox_aug, B, S, mean_std, cfg, seed, nullptr, workspace,
+                              rgb_out, depth_out, depth_raw_out, center_out, K_out, lab, params_out,
+                              p6::stream_of(stream));
+}
+
+extern "C" int pose6d_crop_rgbd_train_indexed_dseed(
+    const uint8_t* rgb_store, int32_t bgr, const uint16_t* depth_store, int64_t n_frames, int32_t H, int32_t W,
+    const int32_t* frame_of, const int32_t* bbox, const float* K, const float* center_tab, const float* quat,
+    const float* trans, const int64_t* obj_id, int64_t n_samples, const int64_t* sample_idx, const int32_t* bbox_aug,
+    int32_t B, int32_t S, const float* mean_std, float brightness, float contrast, float saturation, float hue,
+    float erase_p, float erase_scale_lo, float erase_scale_hi, float erase_ratio_lo, float erase_ratio_hi,
+    const uint64_t* seed, uint8_t* workspace, float* rgb_out, float* depth_out, float* depth_raw_out,
+    float* center_out, float* K_out, float* quat_out, float* trans_out, int64_t* obj_out, float* params_out,
+    int32_t* status, void* stream) {
+  P6_CHECK_INDEXED_ARGS("pose6d_crop_rgbd_train_indexed_dseed");
+  P6_CHECK_ARG(workspace != nullptr && rgb_out != nullptr && seed != nullptr,
+               "pose6d_crop_rgbd_train_indexed_dseed: workspace, rgb_out and seed are required");
+  P6_CHECK_ARG(S <= 232, "pose6d_crop_rgbd_train_indexed_dseed: bad shape (S <= 232: the crop must fit one "
+               "workgroup's LDS)");
+  P6_CHECK_AUG_ARGS("pose6d_crop_rgbd_train_indexed_dseed");
+  if (B == 0) return POSE6D_OK;
+  const StoreTabs t{rgb_store, depth_store, n_frames, n_samples, frame_of, bbox, K, center_tab, quat, trans, obj_id};
+  const LabelOuts lab{quat_out, trans_out, obj_out, status};
+  const AugCfg cfg = aug_cfg(brightness, contrast, saturation, hue, erase_p, erase_scale_lo, erase_scale_hi,
+                             erase_ratio_lo, erase_ratio_hi);
+  return launch_train_indexed(t, bgr, H, W, sample_idx, bbox_aug, B, S, mean_std, cfg, 0, seed, workspace, rgb_out,
+                              depth_out, depth_raw_out, center_out, K_out, lab, params_out, p6::stream_of(stream));
 }

@@ -16,7 +16,9 @@ EpochFeeder  one epoch of batches in torch.utils.data.RandomSampler's order
 
 The per-sample train transform (ColorJitter + RandomErasing) is TrainAugment's, with
 its seed contract unchanged: (seed, rank, calls so far) -> the kernel seed, never
-graph-captured (pose6d/data.py).
+graph-captured (pose6d/data.py).  A planned epoch (pose6d/fit.py) draws those seeds ahead
+of time and goes through `crop_planned`, whose launches read index, boxes and seed from
+device memory and can all be captured.
 """
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -260,11 +262,48 @@ class FrameStore:
              c_o, K_o, q_o, t_o, id_o, self.last_params, self._status, stream())
         return out
 
-    def check(self):
+    def reserve_train(self, B):
+        """The train transform's workspace and parameter buffer for batches of B, allocated
+        here so that crop_planned allocates nothing (pose6d.fit calls it before a capture)."""
+        nws = query("crop_train_workspace", B, self.img_size)
+        if self._ws is None or self._ws.numel() < nws:
+            self._ws = torch.empty(nws, device=self.device, dtype=torch.uint8)
+        if getattr(self, "_plan_params", None) is None or self._plan_params.shape[0] != B:
+            self._plan_params = torch.empty(B, 16, device=self.device)
+
+    def crop_planned(self, sample_idx, bbox_aug, out, augment=None, seed=None):
+        """crop() for a planned epoch (pose6d.fit.EpochPlan): everything is already on the
+        device, nothing is checked, uploaded or allocated here, and every launch can be
+        captured.  sample_idx int64 [B] and bbox_aug int32 [B, 4] (or None) are read at kernel
+        time; out as crop()'s.  augment: a TrainAugment, whose transform then runs with the seed
+        in the DEVICE word `seed` (int64 [1], the kernel's uint64; pose6d_crop_rgbd_train_indexed
+        _dseed) -- augment.next_seed() is the planner's business, not this call's."""
+        B, S = int(sample_idx.shape[0]), self.img_size
+        if self.rgbd:
+            rgb_o, depth_o, raw_o, q_o, t_o, id_o, c_o, K_o = out
+        else:
+            rgb_o, q_o, t_o, id_o, c_o, K_o = out
+            depth_o = raw_o = None
+        store = (self.rgb, int(self.bgr), self.depth, self.n_frames, self.H, self.W, self.frame_of, self.bbox, self.K,
+                 self.center_tab, self.quat, self.trans, self.obj_id, self.n_samples, sample_idx, bbox_aug, B, S,
+                 self._ms)
+        if augment is None:
+            call("crop_rgbd_indexed", *store, rgb_o, depth_o, raw_o, c_o, K_o, q_o, t_o, id_o, self._status, stream())
+            return out
+        if seed is None:
+            raise Pose6dError("FrameStore.crop_planned: the train transform needs the device seed word")
+        self.reserve_train(B)
+        self.last_params = self._plan_params
+        call("crop_rgbd_train_indexed_dseed", *store, *augment.jitter, *augment.erase, seed, self._ws, rgb_o, depth_o,
+             raw_o, c_o, K_o, q_o, t_o, id_o, self.last_params, self._status, stream())
+        return out
+
+    def check(self, status=None):
         """Read the status word of every crop since the last check and reset it; raise
         if a launch met a sample or frame index out of range.  The one host sync of the
-        feed: call it once per epoch."""
-        v = int(self._status.item())
+        feed: call it once per epoch.  status: the word's value when the caller has already
+        read it (pose6d.fit copies it with the epoch's loss table) -- then nothing syncs."""
+        v = int(self._status.item()) if status is None else int(status)
         if v:
             self._status.zero_()
             raise Pose6dError(f"FrameStore.check: a crop read an out-of-range sample or frame index at batch "

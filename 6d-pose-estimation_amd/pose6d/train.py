@@ -164,6 +164,7 @@ class RGBDGeometricTrainer:
         self.wr, self.wt = float(rot_weight), float(trans_weight)
         self.pg = process_group
         self.graphs = None
+        self._before = self._after = None   # capture(before=, after=): launches around the captured step
         self._buckets(bucket_mb, tail_mb)
         # the ADD / ADD-S term of the criterion (models.add_loss.ADDLoss, or None: PoseLoss alone,
         # the launches and bits of a trainer built without it)
@@ -402,23 +403,38 @@ class RGBDGeometricTrainer:
         return self._comm
 
     # ------------------------------------------------------------- graphs
-    def capture(self, data, warmup=2):
+    def capture(self, data, warmup=2, before=None, after=None):
         """Capture the step.  world == 1: one graph.  world > 1: the forward +
         backward as graph segments cut where a gradient bucket completes, and the
-        optimizer as a graph of its own (the all-reduces run between replays)."""
+        optimizer as a graph of its own (the all-reduces run between replays).
+
+        before / after (callables that only launch -- no sync, no upload; pose6d.fit hands
+        in the epoch plan's next batch and the loss append): recorded inside the captured
+        region, in front of the step's first launch and after its last, so one replay is
+        feed + step + bookkeeping.  With segmented graphs they are launched eagerly around
+        step()'s replays instead.  The warm-up steps run them too."""
         self._sync_if_stale()
         self._bind_add_table(capturing=True)
+        self._before, self._after = before, after
         s = torch.cuda.Stream(device=self.dev)
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(warmup):
+                if before is not None:
+                    before()
                 self.step_eager(data)
+                if after is not None:
+                    after()
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         if not self._ddp:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                if before is not None:
+                    before()
                 self.step_body(data, branch=True)
+                if after is not None:
+                    after()
             self.graphs = [g]
         else:
             self.graphs = self._capture_segments(data)
@@ -486,6 +502,8 @@ class RGBDGeometricTrainer:
         if not self._ddp:
             self.graphs[0].replay()
             return
+        if self._before is not None:
+            self._before()
         red = self._red
         red.reset()
         ends = red.ends
@@ -496,6 +514,8 @@ class RGBDGeometricTrainer:
                 red.ready(ends[hi - 1])
         red.finish()
         self.graphs[-1][0].replay()
+        if self._after is not None:
+            self._after()
 
     def snapshot(self):
         """Device copies of everything a step changes (parameters, AdamW moments and

@@ -308,6 +308,48 @@ int pose6d_crop_rgbd_train_indexed(const uint8_t *rgb_store, int32_t bgr, const 
                                    float *K_out, float *quat_out, float *trans_out, int64_t *obj_out,
                                    float *params_out, int32_t *status, void *stream);
 
+/* pose6d_crop_rgbd_train_indexed with the seed in DEVICE memory: `seed` points at one
+ * uint64, read at kernel time and uniform over the launch, so the call can be captured
+ * into a graph and every replay follows later writes to the word.  Everything else --
+ * the device code, the outputs, params_out -- is pose6d_crop_rgbd_train_indexed's: the
+ * same seed value gives the same bits. */
+int pose6d_crop_rgbd_train_indexed_dseed(const uint8_t *rgb_store, int32_t bgr, const uint16_t *depth_store,
+                                         int64_t n_frames, int32_t H, int32_t W, const int32_t *frame_of,
+                                         const int32_t *bbox, const float *K, const float *center_tab,
+                                         const float *quat, const float *trans, const int64_t *obj_id,
+                                         int64_t n_samples, const int64_t *sample_idx, const int32_t *bbox_aug,
+                                         int32_t B, int32_t S, const float *mean_std, float brightness,
+                                         float contrast, float saturation, float hue, float erase_p,
+                                         float erase_scale_lo, float erase_scale_hi, float erase_ratio_lo,
+                                         float erase_ratio_hi, const uint64_t *seed, uint8_t *workspace,
+                                         float *rgb_out, float *depth_out, float *depth_raw_out, float *center_out,
+                                         float *K_out, float *quat_out, float *trans_out, int64_t *obj_out,
+                                         float *params_out, int32_t *status, void *stream);
+
+/* ----------------------------------------------------------------------
+ * The training epoch on the device (the loop of the reference's training scripts,
+ * train_rgbd_geometric.py:92-115): the host plans the epoch once -- which samples, which
+ * jittered boxes, which transform seed each step takes -- and uploads it; a replayed graph
+ * then takes row after row at a device-resident cursor and keeps its loss on the device.
+ * Both entry points run ONE workgroup and are ordered against the calls before and after
+ * them by the stream alone, like pose6d_val_append.
+ *
+ * pose6d_plan_next: idx_plan [steps][B] int64, bbox_plan [steps][B][4] int32 or NULL,
+ * seed_plan [steps] uint64 or NULL; state int64[2] = {cursor, steps refused}.
+ * cursor < steps: row `cursor` is copied to sample_idx [B], bbox_aug [B][4] (required
+ * exactly when bbox_plan is given) and seed_out [1] (required exactly when seed_plan is
+ * given), then cursor += 1.  cursor >= steps (or negative): no output is written and
+ * state[1] += 1.  0 <= B <= 65535, steps >= 0; B == 0 touches nothing. */
+int pose6d_plan_next(const int64_t *idx_plan, const int32_t *bbox_plan, const uint64_t *seed_plan, int64_t steps,
+                     int64_t B, int64_t *state, int64_t *sample_idx, int32_t *bbox_aug, uint64_t *seed_out,
+                     void *stream);
+
+/* pose6d_loss_append: the step's loss (one device fp32) becomes table[rows]; state
+ * int64[3] = {rows, appends refused, non-finite values stored}.  The value's 32 bits are
+ * stored unchanged (NaN payloads, -0.0); a NaN or an infinity also counts in state[2].
+ * rows >= capacity: nothing is written and state[1] += 1.  capacity >= 0. */
+int pose6d_loss_append(const float *loss, float *table, int64_t capacity, int64_t *state, void *stream);
+
 /* ----------------------------------------------------------------------
  * Detection crops -- the per-detection body of the reference's inference scripts up
  * to the model call (scripts/inference/inference_rgbd_geometric.py:110-182; the other
