@@ -1,5 +1,5 @@
 // 3x3 stride-1 convolution with the input patch staged ONCE per 64-channel slice
-// (included by conv_igemm.hip inside its anonymous namespace; uses its Geom,
+// (included by conv_kernels.h inside its anonymous namespace; uses its Geom,
 // conv_epilogue, lds_issue_frags8 and the LDS-DMA helpers of lds_dma.h).
 //
 // The implicit-GEMM kernel (conv_lds_body) streams the A operand once per filter

@@ -475,12 +475,6 @@ int launch_any(const WGeom& g, int bm, int bn, const void* x, const void* dy, fl
   return launch<T, 64, 64>(g, x, dy, ws, s, rj);
 }
 
-int ilog2(int v) {
-  int r = 0;
-  while ((1 << r) < v) ++r;
-  return (1 << r) == v ? r : -1;
-}
-
 }  // namespace
 
 extern "C" int64_t pose6d_conv2d_wgrad_workspace_tuned(int32_t dtype, int32_t N, int32_t Ho, int32_t Wo, int32_t Cin,
@@ -517,31 +511,31 @@ extern "C" int64_t pose6d_conv2d_wgrad_workspace(int32_t dtype, int32_t N, int32
 
 namespace p6 {
 
-WGeom wgrad_geom(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int Ho,
-                 int Wo, WgradPlan* plan_out, const pose6d_tuning_t* tuning) {
+WGeom wgrad_geom(int dtype, const ConvShape& c, WgradPlan* plan_out, const pose6d_tuning_t* tuning) {
   const int bk = dtype == POSE6D_DT_BF16 ? 32 : 16;
   WGeom g{};
-  g.M = N * Ho * Wo; g.Cout = Cout; g.K = KH * KW * Cin; g.Kpad = ceil_div(g.K, bk) * bk;
-  g.SH = H; g.SW = W; g.SC = Cin; g.log2SC = ilog2(Cin); g.RH = Ho; g.RW = Wo;
-  g.KH = KH; g.KW = KW; g.stride = stride; g.pad = pad;
-  g.kwp = KW;
+  g.M = c.N * c.Ho * c.Wo; g.Cout = c.Cout; g.K = c.KH * c.KW * c.Cin; g.Kpad = ceil_div(g.K, bk) * bk;
+  g.SH = c.H; g.SW = c.W; g.SC = c.Cin; g.log2SC = ilog2(c.Cin); g.RH = c.Ho; g.RW = c.Wo;
+  g.KH = c.KH; g.KW = c.KW; g.stride = c.stride; g.pad = c.pad;
+  g.kwp = c.KW;
   // the 4-channel stems: the LDS-DMA body on the row-tap X image (common.h), slabs in
   // row-tap K order (64-column blocks = two kernel rows); the reduce maps them to OIHW.
   // (bf16 fetches two pixels per 16-byte chunk: even W; fp32 one pixel per chunk)
-  if (rowtap_geom(Cin, KH, KW, stride, pad) && Cout % 64 == 0 && (dtype == POSE6D_DT_F32 || (W & 1) == 0)) {
-    const int Kpad = ceil_div(KH * kRowTaps * 4, 64) * 64;
-    const Plan p = plan(dtype, g.M, Cout, Kpad, 64, tuning, true);   // (64: the LDS-DMA channel rule holds)
+  if (rowtap_geom(c.Cin, c.KH, c.KW, c.stride, c.pad) && c.Cout % 64 == 0 &&
+      (dtype == POSE6D_DT_F32 || (c.W & 1) == 0)) {
+    const int Kpad = ceil_div(c.KH * kRowTaps * 4, 64) * 64;
+    const Plan p = plan(dtype, g.M, c.Cout, Kpad, 64, tuning, true);   // (64: the LDS-DMA channel rule holds)
     if (p.fast) {
       g.kwp = kRowTaps;
       g.K = g.Kpad = Kpad;
-      g.gm = ceil_div(Cout, p.bm); g.gn = ceil_div(g.Kpad, p.bn);
+      g.gm = ceil_div(c.Cout, p.bm); g.gn = ceil_div(g.Kpad, p.bn);
       g.splits = p.splits; g.mps = p.mps;
       if (plan_out) *plan_out = p;
       return g;
     }
   }
-  const Plan p = plan(dtype, g.M, Cout, g.Kpad, Cin, tuning, false, KH * KW > 1 || stride > 1);
-  g.gm = ceil_div(Cout, p.bm); g.gn = ceil_div(g.Kpad, p.bn);
+  const Plan p = plan(dtype, g.M, c.Cout, g.Kpad, c.Cin, tuning, false, c.KH * c.KW > 1 || c.stride > 1);
+  g.gm = ceil_div(c.Cout, p.bm); g.gn = ceil_div(g.Kpad, p.bn);
   g.splits = p.splits; g.mps = p.mps;
   if (plan_out) *plan_out = p;
   return g;
@@ -575,24 +569,17 @@ extern "C" int pose6d_conv2d_wgrad_tuned(int32_t dtype, const void* x, const voi
                                          int32_t Cin, int32_t Cin_real, int32_t Cout, int32_t KH, int32_t KW,
                                          int32_t stride, int32_t pad, int32_t Ho, int32_t Wo,
                                          const pose6d_tuning_t* tuning, void* stream) {
+  const p6::ConvShape cs{N, H, W, Cin, Cout, KH, KW, stride, pad, Ho, Wo};
   P6_CHECK_ARG(dtype == POSE6D_DT_F32 || dtype == POSE6D_DT_BF16, "pose6d_conv2d_wgrad: bad dtype %d", dtype);
   P6_CHECK_ARG(ilog2(Cin) >= 2 && Cout % 8 == 0 && Cin_real <= Cin,
                "pose6d_conv2d_wgrad: Cin must be a power of two >= 4");
   Plan p;
-  const WGeom g = p6::wgrad_geom(dtype, N, H, W, Cin, Cout, KH, KW, stride, pad, Ho, Wo, &p, tuning);
+  const WGeom g = p6::wgrad_geom(dtype, cs, &p, tuning);
   P6_CHECK_ARG((int64_t)p.splits * Cout * g.Kpad * 4 <= ws_bytes,
                "pose6d_conv2d_wgrad: workspace %lld bytes < %lld needed (query pose6d_conv2d_wgrad_workspace[_tuned] "
                "with the same tuning)", (long long)ws_bytes, (long long)p.splits * Cout * g.Kpad * 4);
   hipStream_t s = p6::stream_of(stream);
-  int rc;
-  if (p.fast && dtype == POSE6D_DT_F32) {
-    rc = launch_fast_f32_any(p, g, x, dy, workspace, s, ReduceJob{});
-  } else if (p.fast) {
-    rc = launch_fast_any(p, g, x, dy, workspace, s);
-  } else {
-    rc = dtype == POSE6D_DT_BF16 ? launch_any<bf16>(g, p.bm, p.bn, x, dy, workspace, s)
-                                 : launch_any<float>(g, p.bm, p.bn, x, dy, workspace, s);
-  }
+  const int rc = p6::wgrad_launch_carry(dtype, g, p, x, dy, workspace, ReduceJob{}, s);   // (no reduce carried)
   if (rc) return rc;
   return launch_reduce(workspace, dw, Cout, g.Kpad, Cin, Cin_real, KH, KW, g.kwp, g.splits, accumulate, s);
 }

@@ -3,6 +3,7 @@
 // (conv_igemm.hip, pose6d_conv2d_backward).
 #pragma once
 #include "common.h"
+#include "conv_geom.h"
 #include "lds_dma.h"
 
 namespace p6 {
@@ -38,8 +39,7 @@ struct ReduceJob {
 };
 
 // defined in conv_wgrad.hip
-WGeom wgrad_geom(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int Ho,
-                 int Wo, WgradPlan* plan, const pose6d_tuning_t* tuning = nullptr);
+WGeom wgrad_geom(int dtype, const ConvShape& c, WgradPlan* plan, const pose6d_tuning_t* tuning = nullptr);
 int wgrad_reduce_launch(const float* ws, float* dw, int Cout, int Kpad, int SC, int Cin, int KH, int KW, int KWp,
                         int splits,
                         int accumulate, hipStream_t s);
@@ -100,7 +100,7 @@ __device__ __forceinline__ void store_acc_tile(const f32x4 (&acc)[BM / 32][BN / 
 // 64 contiguous channels per X row) are filled by LDS-DMA (8 rows x 128 B per
 // wave instruction, XOR swizzle on the source chunk) through an S-slot ring with
 // counted vmcnt + raw barriers, and read back transposed with ds_read_b64_tr_b16
-// in one asm block per k-half (see lds_read_frags in conv_igemm.hip for why the
+// in one asm block per k-half (see lds_read_frags in conv_kernels.h for why the
 // reads are asm).  Rows past the split's end read the zero page.
 // ============================================================================
 __device__ __forceinline__ int swz_tr4(int r) { return ((((r >> 1) & 1) | (((r >> 3) & 1) << 1)) << 1); }

@@ -35,15 +35,13 @@ def conv_launches(eng, fused=True):
         M = B * op.Ho * op.Wo
         K = op.k * op.k * op.cin
         flops = 2.0 * M * op.cout * K
-        sym = _sym(query("conv_variant", dt, 0, B, op.H, op.W, op.cin_pad, op.cout, op.k, op.k, op.stride, op.pad,
-                         op.Ho, op.Wo), T)
+        sym = _sym(query("conv_variant", dt, 0, *op.shape_args(B)), T)
 
         def fwd(op=op):
-            call("conv2d_fwd", dt, op.src.t, op.wp, op.conv.bias, op.out.t, op.stats, B, op.H, op.W, op.cin_pad,
-                 op.cout, op.k, op.k, op.stride, op.pad, op.Ho, op.Wo, eng.ws_sk, eng.ws_sk_bytes, st)
+            call("conv2d_fwd", dt, op.src.t, op.wp, op.conv.bias, op.out.t, op.stats, *op.shape_args(B), eng.ws_sk,
+                 eng.ws_sk_bytes, st)
         out.append((sym, flops, fwd, op.name + ".fwd"))
-        bv = query("bwd_variant", dt, B, op.H, op.W, op.cin_pad, op.cout, op.k, op.k, op.stride, op.pad, op.Ho,
-                   op.Wo) if (op.needs_dgrad and fused) else 0
+        bv = query("bwd_variant", dt, *op.shape_args(B)) if (op.needs_dgrad and fused) else 0
         if bv:
             # the step's fused data + weight gradient launch (conv2d_backward phase 1;
             # the slab reduce is its own kernel and row in rocprof)
@@ -57,17 +55,14 @@ def conv_launches(eng, fused=True):
 
             def bwd(op=op, dw=dw):
                 call("conv2d_backward_ex", dt, op.src.t, op.out.g, op.wt, None, op.src.g, dw, 0, eng.ws_wgrad,
-                     eng.ws_wgrad.numel() * 4, B, op.H, op.W, op.cin_pad, op.cin, op.cout, op.k, op.k, op.stride,
-                     op.pad, op.Ho, op.Wo, 1, st)
+                     eng.ws_wgrad.numel() * 4, *op.bwd_shape_args(B), 1, st)
             out.append((sym, 2 * flops, bwd, op.name + ".bwd"))
             continue
         if op.needs_dgrad:
-            sym = _sym(query("conv_variant", dt, 1, B, op.H, op.W, op.cin_pad, op.cout, op.k, op.k, op.stride,
-                             op.pad, op.Ho, op.Wo), T)
+            sym = _sym(query("conv_variant", dt, 1, *op.shape_args(B)), T)
 
             def dgrad(op=op):
-                call("conv2d_dgrad", dt, op.out.g, op.wt, None, op.src.g, B, op.H, op.W, op.cin_pad, op.cout, op.k,
-                     op.k, op.stride, op.pad, op.Ho, op.Wo, st)
+                call("conv2d_dgrad", dt, op.out.g, op.wt, None, op.src.g, *op.shape_args(B), st)
             out.append((sym, flops, dgrad, op.name + ".dgrad"))
         v = query("wgrad_variant", dt, M, op.cout, op.k * op.k * op.cin_pad, op.cin_pad)
         if (v >> 8) & 1 and eng.dtype == torch.float32:
@@ -80,8 +75,8 @@ def conv_launches(eng, fused=True):
         dw = torch.empty_like(op.conv.weight)
 
         def wgrad(op=op, dw=dw):
-            call("conv2d_wgrad", dt, op.src.t, op.out.g, dw, 0, eng.ws_wgrad, eng.ws_wgrad.numel() * 4, B, op.H,
-                 op.W, op.cin_pad, op.cin, op.cout, op.k, op.k, op.stride, op.pad, op.Ho, op.Wo, st)
+            call("conv2d_wgrad", dt, op.src.t, op.out.g, dw, 0, eng.ws_wgrad, eng.ws_wgrad.numel() * 4,
+                 *op.bwd_shape_args(B), st)
         out.append((sym + "+reduce", flops, wgrad, op.name + ".wgrad"))
     return out
 

@@ -116,6 +116,16 @@ class _ConvOp:
         self.act_op = None   # the _ActOp applying this conv's BN (set by _ActOp)
         self.needs_dgrad = True
 
+    def shape_args(self, B):
+        """(N, H, W, Cin, Cout, KH, KW, stride, pad, Ho, Wo): the conv's shape at batch B, in
+        the order the C entry points take it (Cin = the padded channel count)."""
+        return (B, self.H, self.W, self.cin_pad, self.cout, self.k, self.k, self.stride, self.pad, self.Ho, self.Wo)
+
+    def bwd_shape_args(self, B):
+        """shape_args with Cin_real after Cin, as the weight-gradient entry points take it."""
+        s = self.shape_args(B)
+        return (*s[:4], self.cin, *s[4:])
+
 
 class _ActOp:
     """out = relu?(bn(y) [+ res_act | + bn_res(y_res)])"""
@@ -246,8 +256,7 @@ class TrunkEngine:
                 op.scale, op.shift, op.mean, op.inv = (f32(op.cout) for _ in range(4))
                 ws_w = max(ws_w, query("conv2d_wgrad_workspace", self.dt, B, op.Ho, op.Wo, op.cin_pad, op.cout, op.k,
                                        op.k))
-                ws_sk = max(ws_sk, query("conv_splitk_workspace", self.dt, 0, B, op.H, op.W, op.cin_pad, op.cout, op.k,
-                                         op.k, op.stride, op.pad, op.Ho, op.Wo))
+                ws_sk = max(ws_sk, query("conv_splitk_workspace", self.dt, 0, *op.shape_args(B)))
                 ws_bn = max(ws_bn, (query("bn_bwd_workspace_rows", M) * 2 + 3) * op.cout)
             elif isinstance(op, _ActOp):
                 residual = op.res_act is not None or op.res_conv is not None
@@ -318,8 +327,7 @@ class TrunkEngine:
             if (p is None or p.pooled or not p.relu or not op.needs_dgrad or len(readers[id(op.src)]) != 1
                     or p.res_act is not None and p.mbits is None or p.res_conv is not None and p.mbits is None):
                 continue
-            rows = query("conv2d_backward_bn_rows", self.dt, B, op.H, op.W, op.cin_pad, op.cout, op.k, op.k,
-                         op.stride, op.pad, op.Ho, op.Wo)
+            rows = query("conv2d_backward_bn_rows", self.dt, *op.shape_args(B))
             if rows <= 0:
                 continue
             c, r = p.cop, p.res_conv
@@ -462,13 +470,11 @@ class TrunkEngine:
                         res, rs, rb = a.res_conv.out.t, a.res_conv.scale, a.res_conv.shift
                     elif a.res_act is not None:
                         res = a.res_act.t
-                    call("conv2d_fwd_act", dt, op.src.t, op.wp, bias, a.out.t, B, op.H, op.W, op.cin_pad, op.cout,
-                         op.k, op.k, op.stride, op.pad, op.Ho, op.Wo, op.scale, op.shift, res, rs, rb, int(a.relu),
-                         self.ws_sk, self.ws_sk_bytes, st)
+                    call("conv2d_fwd_act", dt, op.src.t, op.wp, bias, a.out.t, *op.shape_args(B), op.scale, op.shift,
+                         res, rs, rb, int(a.relu), self.ws_sk, self.ws_sk_bytes, st)
                     continue
-                call("conv2d_fwd", dt, op.src.t, op.wp, bias, op.out.t, op.stats if training else None, B, op.H,
-                     op.W, op.cin_pad, op.cout, op.k, op.k, op.stride, op.pad, op.Ho, op.Wo, self.ws_sk,
-                     self.ws_sk_bytes, st)
+                call("conv2d_fwd", dt, op.src.t, op.wp, bias, op.out.t, op.stats if training else None,
+                     *op.shape_args(B), self.ws_sk, self.ws_sk_bytes, st)
                 if fold:
                     pass
                 elif fused_fin and a is not None and getattr(a, "fin_flags", None) is not None:
@@ -560,8 +566,7 @@ class TrunkEngine:
                   and (r.Ho, r.Wo) == (c3.Ho, c3.Wo) and self.B * c3.Ho * c3.Wo >= min_rows)
             # the dual kernel has no split-K: a pair whose separate launches split K
             # (small grids, long K) stays separate, so both paths agree bit for bit
-            ok = ok and all(query("conv_variant", self.dt, 0, self.B, c.H, c.W, c.cin_pad, c.cout, 1, 1, c.stride, 0,
-                                  c.Ho, c.Wo) >> 16 == 1 for c in (c3, r))
+            ok = ok and all(query("conv_variant", self.dt, 0, *c.shape_args(self.B)) >> 16 == 1 for c in (c3, r))
             if ok:
                 pairs[c3] = r
                 pairs[r] = None
@@ -673,19 +678,12 @@ class TrunkEngine:
                 # data + weight gradient: one fused launch on the bf16 fast path
                 ws = ws_pp[slot]
                 dw = grad_of(op.conv.weight)
-                args = (dt, op.src.t, dy, op.wt, dres, dx, dw, acc, ws, ws.numel() * 4, B, op.H, op.W, op.cin_pad,
-                        op.cin, op.cout, op.k, op.k, op.stride, op.pad, op.Ho, op.Wo)
-                job = _WgradReduce(ws.data_ptr(), dw.data_ptr(), dt, B, op.H, op.W, op.cin_pad, op.cin, op.cout,
-                                   op.k, op.k, op.stride, op.pad, op.Ho, op.Wo, acc)
+                shape = op.bwd_shape_args(B)
+                job = _WgradReduce(ws.data_ptr(), dw.data_ptr(), dt, *shape, acc)
                 prev = ctypes.addressof(pending) if pending is not None else None
-                if op.bnr_desc is not None and self.bwd_conv_bn_reduce:
-                    call("conv2d_backward_chain_bn", dt, op.src.t, dy, op.wt, dres, dmask, *args[5:], prev,
-                         ctypes.addressof(deferred), ctypes.addressof(op.bnr_desc), st)
-                elif dmask is not None:
-                    call("conv2d_backward_chain_masked", dt, op.src.t, dy, op.wt, dres, dmask, *args[5:], prev,
-                         ctypes.addressof(deferred), st)
-                else:
-                    call("conv2d_backward_chain", *args, prev, ctypes.addressof(deferred), st)
+                bnr = op.bnr_desc if self.bwd_conv_bn_reduce else None
+                call("conv2d_backward_chain_bn", dt, op.src.t, dy, op.wt, dres, dmask, dx, dw, acc, ws, ws.numel() * 4,
+                     *shape, prev, ctypes.addressof(deferred), ctypes.addressof(bnr) if bnr is not None else None, st)
                 if pending_op is not None:
                     conv_done(pending_op)          # its reduce ran in this launch (or just before it)
                 if deferred.value:

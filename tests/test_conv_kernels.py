@@ -30,7 +30,7 @@ def _close(got, ref, rtol, what):
 
 
 def test_s2_class_order_rotation():
-    """The stride-2 data gradient's workgroup -> (tile, parity class) map (conv_igemm.hip,
+    """The stride-2 data gradient's workgroup -> (tile, parity class) map (conv_kernels.h,
     conv_lds_body): logical ids 4t .. 4t+3 are tile t's four classes (a permutation,
     so every output pixel is written exactly once, as before), and the class at each
     position mod 4 -- the shader engine a dispatch round-robin hands it to -- rotates

@@ -4,8 +4,8 @@ Host-only plan queries (no device): for every distinct conv geometry of the four
 trunks (the ResNet50 trunk they share and the z-CNN of the RGB-Geometric model) at a
 224x224 input, at batch 1, 2, 8 and 32, fp32 and bf16, the forward / data-gradient
 variant, the forward split-K workspace, the patch plan, the weight-gradient variant and
-workspace (which exposes the split count) and the fused-backward variant must equal
-tests/golden/conv_plans.json.  A change to a planning rule has to update that table on
+workspace (which exposes the split count), the fused-backward variant and the row count
+of the backward's BatchNorm-reduce partials must equal tests/golden/conv_plans.json.  A change to a planning rule has to update that table on
 purpose: run this file as a script against the library whose plans are the new truth,
 
     POSE6D_LIB=/path/to/libpose6d.so python tests/test_conv_plans.py
@@ -21,7 +21,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(REPO, "tests", "golden", "conv_plans.json")
 BATCHES = (1, 2, 8, 32)
 QUERIES = ("fwd_variant", "dgrad_variant", "fwd_splitk_workspace", "patch_plan", "wgrad_variant", "wgrad_workspace",
-           "bwd_variant")
+           "bwd_variant", "bwd_bn_rows")
 
 
 def trunk_geometries():
@@ -62,7 +62,8 @@ def plan_table():
                     query("conv_patch_plan", dt, *conv),
                     query("wgrad_variant", dt, B * Ho * Wo, cout, k * k * cin, cin),
                     query("conv2d_wgrad_workspace", dt, B, Ho, Wo, cin, cout, k, k),
-                    query("bwd_variant", dt, *conv))))
+                    query("bwd_variant", dt, *conv),
+                    query("conv2d_backward_bn_rows", dt, *conv))))
     return table
 
 
