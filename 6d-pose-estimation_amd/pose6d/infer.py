@@ -14,7 +14,10 @@ utils/mesh_utils.py:7-53).  Here:
   PoseEstimator    (1) -> eval forward of one of the four drop-in models -> (3) + (4) in
                    one fp64 launch (pose6d_pose_project), replayed from one hipGraph per
                    detection-count bucket;
-  load_mesh_corners / DEFAULT_K   the host helpers the scripts import.
+  load_mesh_corners / DEFAULT_K   the host helpers the scripts import;
+  DepthRefiner     (not in the reference) point-to-point ICP of the N poses against the
+                   depth frame in ONE launch (pose6d_depth_refine); PoseEstimator(refine=)
+                   appends it and a projection of the refined pose to the same graph.
 
 This is NOT CropRGBD on a detector box.  The scripts differ from the training dataset
 (data/dataset_rgbd.py) in three ways, all kept:
@@ -82,6 +85,55 @@ def load_mesh_corners(mesh_dir, obj_id_str):
     sel = ((0, 0, 0), (1, 0, 0), (1, 1, 0), (0, 1, 0), (0, 0, 1), (1, 0, 1), (1, 1, 1), (0, 1, 1))
     ends = (lo, hi)
     return np.array([[ends[s[a]][a] for a in range(3)] for s in sel])
+
+
+def load_mesh_points(mesh_dir, obj_id_str, n_points=1500, seed=0):
+    """(points (n, 3) float32 metres, diameter metres) of an object for DepthRefiner, from
+    the `obj_<id>.ply` load_mesh_corners reads: the header's `element vertex` count of
+    vertex lines (all lines of three or more numbers when the header gives none), mm -> m,
+    a seeded subsample of n_points without replacement when the mesh has more.  The
+    diameter is models_info.yml's (mm) when the file lists the object, else the exact
+    largest pairwise distance of the subsample.  None for a missing or empty mesh."""
+    path = os.path.join(mesh_dir, f"obj_{obj_id_str}.ply")
+    if not os.path.exists(path):
+        return None
+    rows, body, count = [], False, None
+    with open(path, "r") as f:
+        for line in f:
+            if not body:
+                v = line.split()
+                if len(v) == 3 and v[0] == "element" and v[1] == "vertex":
+                    count = int(v[2])
+                body = "end_header" in line
+                continue
+            if count is not None and len(rows) >= count:
+                break
+            v = line.split()
+            if len(v) >= 3:
+                rows.append((float(v[0]), float(v[1]), float(v[2])))
+    verts = np.array(rows, dtype=np.float64).reshape(-1, 3) / 1000.0
+    if len(verts) == 0:
+        return None
+    if len(verts) > n_points:
+        verts = verts[np.random.default_rng(seed).choice(len(verts), int(n_points), replace=False)]
+    pts = verts.astype(np.float32)
+    diameter = None
+    info_path = os.path.join(mesh_dir, "models_info.yml")
+    if os.path.exists(info_path):
+        import yaml
+        with open(info_path, "r") as f:
+            info = yaml.safe_load(f) or {}
+        for key, data in info.items():
+            try:
+                if int(key) == int(obj_id_str) and "diameter" in data:
+                    diameter = float(data["diameter"]) / 1000.0
+            except (TypeError, ValueError):
+                pass
+    if diameter is None:
+        p = pts.astype(np.float64)
+        diameter = max(float(np.sqrt(((p[s:s + 256, None] - p[None]) ** 2).sum(-1).max()))
+                       for s in range(0, len(p), 256))
+    return pts, diameter
 
 
 def _host_boxes(boxes):
@@ -311,18 +363,139 @@ class PoseResult:
         return PoseResult(self._buf.clone(), self._bucket, self.n)
 
 
+RefineOutput = namedtuple("RefineOutput", "quat trans quat32 trans32 n_corr rms refined pose_trace corr samples")
+
+
+class DepthRefiner:
+    """Point-to-point ICP of estimated poses against the depth frame, one
+    pose6d_depth_refine launch for N detections (DESIGN.md "Depth refinement").
+
+    points: {key: (n, 3) metres}, diameters: {key: metres} (load_mesh_points' results), the
+    keys those of the estimator's `corners` dict.  grid: samples per box side (G, P = G * G
+    per box, 1..32); iters: fixed iteration count (1..64); gate / trim: fractions of the
+    object's diameter -- samples farther than gate * diameter from the initial translation
+    are background, pairs farther apart than trim * diameter are dropped; min_points: the
+    fewest accepted pairs an update needs (>= 3).  The mesh table is packed in
+    models.add_loss._MeshTable's layout, once per device.
+
+    __call__(depth, boxes, obj, quat, trans, frame_of=None, K=DEFAULT_K, trace=False, out=None),
+    all device tensors: depth (F, H, W) / (H, W) uint16; boxes (N, 4) int32; obj (N,) int64
+    slots (slots(keys) maps keys, -1 = no mesh); quat (N, 4) fp32 (x, y, z, w); trans (N, 3)
+    float64; frame_of (N,) int32 or None; K (3, 3) / (F, 3, 3) or _k_dev's pair.  Returns a
+    RefineOutput: quat (N, 4) / trans (N, 3) f64, their fp32 casts quat32 / trans32, n_corr
+    (N,) i32, rms (N, 2) f64, refined (N,) u8 and, with trace=True, pose_trace (N, iters + 1,
+    7) f64, corr (N, iters, P) i32 and samples (N, P, 3) f64 (None otherwise).  out: the
+    seven result tensors to write into (a captured graph's static buffers)."""
+
+    def __init__(self, points, diameters, grid=32, iters=10, gate=0.75, trim=0.25, min_points=16, depth_scale=0.001):
+        keys = [k for k, v in points.items() if v is not None]
+        self._slot = {k: i for i, k in enumerate(keys)}
+        self._points = [np.array(points[k], np.float32).reshape(-1, 3) for k in keys]   # (copies)
+        missing = [k for k in keys if k not in diameters]
+        if missing:
+            raise Pose6dError(f"DepthRefiner: no diameter for {missing}")
+        self._diam = [float(diameters[k]) for k in keys]
+        self.grid, self.iters, self.min_points = int(grid), int(iters), int(min_points)
+        self.gate, self.trim, self.depth_scale = float(gate), float(trim), float(depth_scale)
+        self._tables = {}
+
+    def slots(self, keys):
+        """Mesh-table slots (int64 array) of a sequence of keys; -1 for a key without a mesh."""
+        return np.array([self._slot.get(k, -1) for k in keys], np.int64)
+
+    def table(self, dev):
+        T = self._tables.get(dev)
+        if T is None:
+            from models.add_loss import _MeshTable
+            pts = {i: torch.from_numpy(p) for i, p in enumerate(self._points)}
+            T = self._tables[dev] = _MeshTable(pts, dict(enumerate(self._diam)), dev)
+        return T
+
+    def empty_outputs(self, N, dev):
+        e = lambda dt, *s: torch.empty(*s, device=dev, dtype=dt)
+        return (e(torch.float64, N, 4), e(torch.float64, N, 3), e(torch.float32, N, 4), e(torch.float32, N, 3),
+                e(torch.int32, N), e(torch.float64, N, 2), e(torch.uint8, N))
+
+    def __call__(self, depth, boxes, obj, quat, trans, frame_of=None, K=DEFAULT_K, trace=False, out=None):
+        require_device(depth, boxes, obj, quat, trans, frame_of)
+        dev = quat.device
+        if depth.dim() == 2:
+            depth = depth[None]
+        if depth.dtype != torch.uint16 or depth.dim() != 3:
+            raise Pose6dError(f"DepthRefiner: depth must be (F, H, W) uint16, got {tuple(depth.shape)} {depth.dtype}")
+        F, H, W = depth.shape
+        N = quat.shape[0]
+        q = quat.detach().to(torch.float32).contiguous()
+        t = trans.detach().to(torch.float64).contiguous()
+        if q.shape != (N, 4) or t.shape != (N, 3) or obj.numel() != N or tuple(boxes.shape) != (N, 4):
+            raise Pose6dError("DepthRefiner: boxes (N, 4), obj (N,), quat (N, 4) and trans (N, 3) must agree")
+        fo = frame_of.to(torch.int32).contiguous() if frame_of is not None else None
+        if fo is not None and fo.numel() != N:
+            raise Pose6dError(f"DepthRefiner: frame_of must have one entry per box ({N}), got {fo.numel()}")
+        Kd, per_frame = K if isinstance(K, tuple) else _k_dev(K, dev)
+        if per_frame and Kd.shape[0] < F:
+            raise Pose6dError(f"DepthRefiner: per-frame K must have {F} rows, got {Kd.shape[0]}")
+        T = self.table(dev)
+        if out is None:
+            out = self.empty_outputs(N, dev)
+        P = self.grid * self.grid
+        dbg = (None, None, None)
+        if trace:
+            dbg = (torch.empty(N, self.iters + 1, 7, device=dev, dtype=torch.float64),
+                   torch.empty(N, self.iters, P, device=dev, dtype=torch.int32),
+                   torch.empty(N, P, 3, device=dev, dtype=torch.float64))
+        call("depth_refine", depth.contiguous(), F, H, W, self.depth_scale, Kd, per_frame,
+             boxes.to(torch.int32).contiguous(), fo, obj.to(torch.int64).contiguous(), T.points, T.off, T.npts, T.diam,
+             T.n_slots, q, t, N, self.grid, self.iters, self.gate, self.trim, self.min_points, *out, *dbg, stream())
+        return RefineOutput(*out, *dbg)
+
+
+class RefinedPoseResult(PoseResult):
+    """A PoseResult plus the depth-refined pose (PoseEstimator(refine=...)): quat_ref (N, 4)
+    f64 (x, y, z, w; unit, w >= 0) and trans_ref (N, 3) f64; points_ref / pixels_ref (and
+    box2d_ref, axes2d_ref): the projection of the refined pose; n_corr (N,) i32 accepted
+    pairs of the last iteration, rms (N, 2) f64 their root-mean-square distance in the first
+    and the last iteration (m), refined (N,) bool: False where the refinement had nothing to
+    work with (no mesh, zero depth in the box, too few pairs) -- quat_ref / trans_ref are
+    then the network's pose.  A buffer layout of its own: PoseResult's fields first."""
+
+    _FIELDS = PoseResult._FIELDS + (
+        ("quat_ref", torch.float64, (4,)), ("trans_ref", torch.float64, (3,)),
+        ("points_ref", torch.float64, (N_POINTS, 2)), ("pixels_ref", torch.int64, (N_POINTS, 2)),
+        ("n_corr", torch.int32, ()), ("rms", torch.float64, (2,)), ("refined", torch.uint8, ()),
+        ("quat32_ref", torch.float32, (4,)), ("trans32_ref", torch.float32, (3,)))   # what the projection read
+
+    quat_ref = property(lambda s: s._quat_ref[:s.n])
+    trans_ref = property(lambda s: s._trans_ref[:s.n])
+    points_ref = property(lambda s: s._points_ref[:s.n])
+    pixels_ref = property(lambda s: s._pixels_ref[:s.n])
+    box2d_ref = property(lambda s: s._pixels_ref[:s.n, :8])
+    axes2d_ref = property(lambda s: s._pixels_ref[:s.n, 8:])
+    n_corr = property(lambda s: s._n_corr[:s.n])
+    rms = property(lambda s: s._rms[:s.n])
+    refined = property(lambda s: s._refined[:s.n].bool())
+
+    def cpu(self):
+        return RefinedPoseResult(self._buf.cpu(), self._bucket, self.n)
+
+    def clone(self):
+        return RefinedPoseResult(self._buf.clone(), self._bucket, self.n)
+
+
 class _Bucket:
     """The static buffers and (graph=True) the captured graph of one (detections bucket,
     depth present) pair."""
 
-    def __init__(self, B, dev, cropper):
+    def __init__(self, B, dev, cropper, result=PoseResult):
         self.B = B
         self.boxes = torch.zeros(B, 4, dtype=torch.int32, device=dev)
         self.frame_of = torch.zeros(B, dtype=torch.int32, device=dev)
         self.obj = torch.zeros(B, dtype=torch.int64, device=dev)
+        if result is not PoseResult:   # the refiner's mesh-table slots
+            self.obj_ref = torch.zeros(B, dtype=torch.int64, device=dev)
         self.crops = cropper.empty_outputs(B, dev)
-        self.out = torch.zeros(PoseResult.nbytes(B), dtype=torch.uint8, device=dev)
-        self.res = PoseResult(self.out, B, B)
+        self.out = torch.zeros(result.nbytes(B), dtype=torch.uint8, device=dev)
+        self.res = result(self.out, B, B)
         self.engines = {}    # this bucket's own engines: their buffers are sized by the batch
         self.graph = None
 
@@ -353,10 +526,14 @@ class PoseEstimator:
     refresh() after writing the model's weights (a replay runs no Python that could notice).
     The model stays usable on its own: the estimator swaps a bucket's engines in around
     each of its calls and restores the model's own afterwards.
+    refine: a DepthRefiner (keyed like `corners`) or None.  With one, the body becomes crop
+    -> forward -> projection -> refinement of (quat, trans_cam) against the depth frame ->
+    projection of the refined pose, all in the same graph, and the result is a
+    RefinedPoseResult; a call without depth raises.  None: nothing changes.
     """
 
     def __init__(self, model, corners, K=DEFAULT_K, class_to_obj=None, max_detections=32, max_frames=1, graph=True,
-                 dataset_intrinsics=False, img_size=224, bgr=False, axis_scale=0.1):
+                 dataset_intrinsics=False, img_size=224, bgr=False, axis_scale=0.1, refine=None):
         kind = type(model).__name__
         if kind not in _KINDS:
             raise Pose6dError(f"PoseEstimator: model must be one of {sorted(_KINDS)}, got {kind}")
@@ -374,6 +551,10 @@ class PoseEstimator:
         self.max_detections, self.max_frames = int(max_detections), int(max_frames)
         self.graph = bool(graph)
         self.axis_scale = float(axis_scale)
+        if refine is not None and not isinstance(refine, DepthRefiner):
+            raise Pose6dError("PoseEstimator: refine must be a DepthRefiner or None")
+        self.refine = refine
+        self._result = PoseResult if refine is None else RefinedPoseResult
         self.cropper = CropDetections(img_size, True, bgr, dataset_intrinsics)
         if isinstance(corners, dict):
             keys = [k for k, v in corners.items() if v is not None]
@@ -432,6 +613,11 @@ class PoseEstimator:
             rows[i] = self._row.get(key, -1)
         return rows
 
+    def _ref_objs(self, classes):
+        """The refiner's mesh-table slot of every detection (-1: no mesh, passed through)."""
+        c = np.asarray(classes.cpu().numpy() if isinstance(classes, torch.Tensor) else classes).reshape(-1)
+        return self.refine.slots([k if self.class_to_obj is None else self.class_to_obj.get(k) for k in c.tolist()])
+
     def _stage_frames(self, rgb, depth):
         dev = self.device
         rgb = rgb if isinstance(rgb, torch.Tensor) else torch.from_numpy(np.require(rgb, requirements="CW"))
@@ -471,6 +657,15 @@ class PoseEstimator:
         pose_project(res._quat, res._trans, self._K, bk.obj, self.corners,
                      boxes=bk.boxes if self.corrects_translation else None, frame_of=bk.frame_of,
                      axis_scale=self.axis_scale, out=(res._trans_cam, res._points, res._pixels, res._valid))
+        if self.refine is not None:
+            # the network's pose (the translation the projection used) against the depth frame,
+            # then the projection of the refined pose: two more launches in the same graph
+            self.refine(self._depth, bk.boxes, bk.obj_ref, res._quat, res._trans_cam, frame_of=bk.frame_of, K=self._K,
+                        out=(res._quat_ref, res._trans_ref, res._quat32_ref, res._trans32_ref, res._n_corr, res._rms,
+                             res._refined))
+            pose_project(res._quat32_ref, res._trans32_ref, self._K, bk.obj, self.corners, boxes=None,
+                         frame_of=bk.frame_of, axis_scale=self.axis_scale,
+                         out=(None, res._points_ref, res._pixels_ref, None))
 
     def __call__(self, rgb, depth, boxes, classes, frame_of=None):
         if self.model.training:
@@ -479,23 +674,28 @@ class PoseEstimator:
         N = bx.shape[0]
         if N > self.max_detections:
             raise Pose6dError(f"PoseEstimator: {N} detections, max_detections = {self.max_detections}")
+        if self.refine is not None and depth is None:
+            raise Pose6dError("PoseEstimator: refine= needs the depth frame (depth=None given)")
         if N == 0:
-            return PoseResult(torch.zeros(PoseResult.nbytes(1), dtype=torch.uint8, device=self.device), 1, 0)
+            return self._result(torch.zeros(self._result.nbytes(1), dtype=torch.uint8, device=self.device), 1, 0)
         B = next(b for b in BUCKETS if b >= N)
         rgb_frames = rgb.shape[0] if rgb.ndim == 4 else 1
         fo = np.zeros(N, np.int64) if frame_of is None else _host_frame_of(frame_of, N, rgb_frames)
         rows = self._objs(classes, N)
+        ref_rows = self._ref_objs(classes) if self.refine is not None else None
         F = self._stage_frames(rgb, depth)
         assert F == rgb_frames
         has_depth = depth is not None
         bk = self._buckets.get((B, has_depth))
         if bk is None:
-            bk = self._buckets[(B, has_depth)] = _Bucket(B, self.device, self.cropper)
+            bk = self._buckets[(B, has_depth)] = _Bucket(B, self.device, self.cropper, self._result)
         # pad by repeating detection 0; one small host -> device copy per table
         pad = lambda a: np.concatenate([a, np.repeat(a[:1], B - N, axis=0)]) if B > N else a
         bk.boxes.copy_(torch.from_numpy(pad(bx).astype(np.int32)), non_blocking=True)
         bk.frame_of.copy_(torch.from_numpy(pad(fo).astype(np.int32)), non_blocking=True)
         bk.obj.copy_(torch.from_numpy(pad(rows)), non_blocking=True)
+        if ref_rows is not None:
+            bk.obj_ref.copy_(torch.from_numpy(pad(ref_rows)), non_blocking=True)
         own, self.model._p6_engines = self.model._p6_engines, bk.engines
         try:
             with torch.no_grad():
@@ -507,7 +707,7 @@ class PoseEstimator:
                     bk.graph.replay()
         finally:
             self.model._p6_engines = own
-        return PoseResult(bk.out, B, N)
+        return self._result(bk.out, B, N)
 
     def _capture(self, bk, has_depth):
         s = torch.cuda.Stream(device=self.device)

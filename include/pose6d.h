@@ -415,6 +415,50 @@ int pose6d_pose_project(const float *quat, const float *trans, const int32_t *bo
                         const double *corners, int64_t n_obj, double axis_scale, int32_t N, double *trans_out,
                         double *pts_out, int64_t *pix_out, uint8_t *valid_out, void *stream);
 
+/* ----------------------------------------------------------------------
+ * Depth refinement: point-to-point ICP of N estimated poses against the depth frame
+ * their detections were cropped from, ONE launch, one workgroup per detection.  The
+ * reference project has no such step; the arithmetic contract below is restated in
+ * fp64 numpy by tests/refine_ref.py.
+ * depth [F][H][W] uint16 raw units, metres = d * depth_scale; K double [9] or [F][9]
+ * with frame_of (K_per_frame as pose6d_pose_project); boxes_xyxy [N][4] int32; frame_of
+ * [N] int32 or NULL (frame 0); obj [N] int64 slots of the packed mesh table points /
+ * off / npts / diam / n_slots of pose6d_add_eval; quat [N][4] fp32 (x, y, z, w), model
+ * -> camera, normalised in double here; trans [N][3] double.
+ * Samples: G x G per box, sample k = j * G + i at pixel u = x1 + floor((2i + 1)(x2 -
+ * x1) / (2G)), v alike from j, y1, y2 (integers).  Valid inside the frame with depth >
+ * 0; back-projected in double, z = d * depth_scale, x = (u - cx) * z / fx, y alike,
+ * every product rounded on its own; kept when sqrt(|p - trans|^2) <= gate * diam -- the
+ * gate centre is the INITIAL translation in every iteration.
+ * `iters` times: q = R^T (p - t) in double, rounded to fp32; the nearest mesh point by
+ * direct fp32 differences s = fma(dz, dz, fma(dy, dy, dx * dx)), first index on a tie;
+ * accepted when sqrt((double)s) <= trim * diam; over the accepted pairs n, sum p, sum m,
+ * sum m p^T in double (p relative to the initial translation) in a fixed order; n <
+ * min_points stops and keeps the last pose; else Horn's closed form (cyclic Jacobi on
+ * the 4 x 4 symmetric matrix, a fixed number of sweeps) gives a unit quaternion, w >=
+ * 0, hence a proper rotation, and t = mean p - R mean m.
+ * Outputs: quat_out [N][4] double (unit, w >= 0), trans_out [N][3] double, quat32_out /
+ * trans32_out their float casts (may be NULL), n_corr [N] int32 (accepted pairs of the
+ * last completed iteration), rms [N][2] double (root mean square accepted distance of
+ * the first and the last completed iteration), refined [N] uint8.  refined = 0 with the
+ * input pose passed through (the quaternion normalised where it can be) and zeros
+ * elsewhere: obj outside the table or without points, a zero / NaN quaternion, frame_of
+ * outside [0, F), fewer than min_points accepted pairs in the first iteration.
+ * Debug outputs, NULL in the product path: pose_trace [N][iters + 1][7] double (x, y,
+ * z, w, tx, ty, tz before iteration 0 and after each; the last pose repeats after a
+ * stop), corr_out [N][iters][P] int32 (the accepted mesh index; -1 invalid, gated out
+ * or trimmed; -2 iteration not completed), samples_out [N][P][3] double (the kept
+ * samples' camera points, NaN for the others).
+ * G in [1, 32], iters in [1, 64], min_points >= 3, gate, trim, depth_scale > 0.
+ * ---------------------------------------------------------------------- */
+int pose6d_depth_refine(const uint16_t *depth, int32_t F, int32_t H, int32_t W, double depth_scale, const double *K,
+                        int32_t K_per_frame, const int32_t *boxes_xyxy, const int32_t *frame_of, const int64_t *obj,
+                        const float *points, const int32_t *off, const int32_t *npts, const double *diam,
+                        int32_t n_slots, const float *quat, const double *trans, int32_t N, int32_t G, int32_t iters,
+                        double gate, double trim, int32_t min_points, double *quat_out, double *trans_out,
+                        float *quat32_out, float *trans32_out, int32_t *n_corr, double *rms, uint8_t *refined,
+                        double *pose_trace, int32_t *corr_out, double *samples_out, void *stream);
+
 /* ------------------------------------------------------------------------
  * ResNet50 trunk — replaces torchvision.models.resnet50 children[:-1] as
  * wrapped by every model (pose_net_rgb.py:18-20, pose_net_rgb_geometric.py:18-20,

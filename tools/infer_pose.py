@@ -13,6 +13,10 @@ cv2.imread's); a missing depth image gives zeros like the scripts.  The checkpoi
 reference's torch.save dict, opened with weights_only=True.  Output: JSON, one entry per
 detection with the quaternion (x, y, z, w), the translation the projection used, the 8
 projected box corners, the 4 axis points (origin, x, y, z) and `valid` (false: no mesh).
+--refine (needs --depth) refines every pose against the depth frame (pose6d.infer.DepthRefiner:
+point-to-point ICP on --refine-points mesh points for --refine-iters iterations) and adds
+per detection `quat_ref_xyzw`, `trans_ref_m`, `box2d_ref`, `axes2d_ref`, `n_corr`, `rms_m`
+(first and last iteration) and `refined`; without the flag the output is unchanged.
 """
 import argparse
 import json
@@ -42,8 +46,11 @@ def main(argv=None):
     ap.add_argument("--dataset-intrinsics", action="store_true",
                     help="feed the model the training dataset's crop intrinsics, not the scripts'")
     ap.add_argument("--bf16", action="store_true")
+    ap.add_argument("--refine", action="store_true", help="refine the poses against the depth frame (ICP)")
+    ap.add_argument("--refine-iters", type=int, default=10)
+    ap.add_argument("--refine-points", type=int, default=1500, help="mesh points per object")
     a = ap.parse_args(argv)
-    from pose6d.infer import DEFAULT_K, PoseEstimator, load_mesh_corners
+    from pose6d.infer import DEFAULT_K, DepthRefiner, PoseEstimator, load_mesh_corners, load_mesh_points
     from pose6d.linemod import load_depth, load_rgb
     from tools.compare_models import load_model
 
@@ -51,6 +58,9 @@ def main(argv=None):
         dets = json.load(f)
     rgb = load_rgb(a.image)
     depth = load_depth(a.depth, rgb.shape[:2]) if a.depth else None
+    if a.refine and depth is None:
+        print("Error: --refine needs --depth", file=sys.stderr)
+        return 1
     if a.model in ("RGBD", "RGBD-Geometric") and depth is None:
         print("Warning: no depth image, using zeros", file=sys.stderr)
         depth = np.zeros(rgb.shape[:2], np.uint16)
@@ -62,8 +72,14 @@ def main(argv=None):
         model.set_compute_dtype(torch.bfloat16)
     corners = {name: load_mesh_corners(a.mesh_dir, name) for name in sorted(set(CLASS_ID_TO_OBJ_NAME.values()))}
     names = [CLASS_ID_TO_OBJ_NAME.get(int(d["cls"]), "01") for d in dets]
+    refine = None
+    if a.refine:
+        meshes = {name: load_mesh_points(a.mesh_dir, name, n_points=a.refine_points) for name in corners}
+        meshes = {k: v for k, v in meshes.items() if v is not None}
+        refine = DepthRefiner({k: v[0] for k, v in meshes.items()}, {k: v[1] for k, v in meshes.items()},
+                              iters=a.refine_iters)
     est = PoseEstimator(model, corners, K=DEFAULT_K, max_detections=32, graph=False,
-                        dataset_intrinsics=a.dataset_intrinsics)
+                        dataset_intrinsics=a.dataset_intrinsics, refine=refine)
     out = []
     for s in range(0, len(dets), 32):   # the scripts have no limit; the estimator takes 32 at a time
         part = dets[s:s + 32]
@@ -73,6 +89,11 @@ def main(argv=None):
                         "xyxy": [int(v) for v in d["xyxy"]], "valid": bool(res.valid[i]),
                         "quat_xyzw": res.quat[i].tolist(), "trans_m": res.trans_cam[i].tolist(),
                         "box2d": res.box2d[i].tolist(), "axes2d": res.axes2d[i].tolist()})
+            if a.refine:
+                out[-1].update({"quat_ref_xyzw": res.quat_ref[i].tolist(), "trans_ref_m": res.trans_ref[i].tolist(),
+                                "box2d_ref": res.box2d_ref[i].tolist(), "axes2d_ref": res.axes2d_ref[i].tolist(),
+                                "n_corr": int(res.n_corr[i]), "rms_m": res.rms[i].tolist(),
+                                "refined": bool(res.refined[i])})
     est.check()
     text = json.dumps({"image": a.image, "model": a.model, "poses": out}, indent=1)
     if a.out:
