@@ -17,7 +17,11 @@ utils/mesh_utils.py:7-53).  Here:
   load_mesh_corners / DEFAULT_K   the host helpers the scripts import;
   DepthRefiner     (not in the reference) point-to-point ICP of the N poses against the
                    depth frame in ONE launch (pose6d_depth_refine); PoseEstimator(refine=)
-                   appends it and a projection of the refined pose to the same graph.
+                   appends it and a projection of the refined pose to the same graph;
+  PoseVerifier     (not in the reference) render-and-compare of the N poses against the depth
+                   frame in ONE launch (pose6d_pose_verify): a confidence per pose and, with
+                   refine=, the choice between the network's pose and the refined one;
+                   PoseEstimator(verify=) appends it to the same graph.
 
 This is NOT CropRGBD on a detector box.  The scripts differ from the training dataset
 (data/dataset_rgbd.py) in three ways, all kept:
@@ -31,6 +35,7 @@ This is NOT CropRGBD on a detector box.  The scripts differ from the training da
 
 No detector is built (YOLO stays out of scope: DESIGN.md); boxes come from the caller.
 """
+import functools
 import os
 from collections import namedtuple
 
@@ -117,6 +122,15 @@ def load_mesh_points(mesh_dir, obj_id_str, n_points=1500, seed=0):
     if len(verts) > n_points:
         verts = verts[np.random.default_rng(seed).choice(len(verts), int(n_points), replace=False)]
     pts = verts.astype(np.float32)
+    diameter = _info_diameter(mesh_dir, obj_id_str)
+    if diameter is None:
+        diameter = _largest_distance(pts)
+    return pts, diameter
+
+
+def _info_diameter(mesh_dir, obj_id_str):
+    """The object's diameter (m) from mesh_dir/models_info.yml (mm), None when the file or the
+    entry is missing."""
     diameter = None
     info_path = os.path.join(mesh_dir, "models_info.yml")
     if os.path.exists(info_path):
@@ -129,11 +143,55 @@ def load_mesh_points(mesh_dir, obj_id_str, n_points=1500, seed=0):
                     diameter = float(data["diameter"]) / 1000.0
             except (TypeError, ValueError):
                 pass
+    return diameter
+
+
+def _largest_distance(pts):
+    """The exact largest pairwise distance of fp32 points, in double."""
+    p = pts.astype(np.float64)
+    return max(float(np.sqrt(((p[s:s + 256, None] - p[None]) ** 2).sum(-1).max())) for s in range(0, len(p), 256))
+
+
+def load_mesh_triangles(mesh_dir, obj_id_str):
+    """(verts (V, 3) float32 metres, faces (T, 3) int32, diameter metres) of an object for
+    PoseVerifier, from the ASCII `obj_<id>.ply`: the header's `element vertex` count of vertex
+    lines (mm -> m), then its `element face` count of face lines `k i0 i1 ... i(k-1)`; a
+    polygon of more than three vertices is fanned from its first, (i0, ij, ij+1).  The
+    diameter is load_mesh_points': models_info.yml's when the file lists the object, else the
+    exact largest pairwise vertex distance.  None for a missing mesh or one without vertices
+    or faces."""
+    path = os.path.join(mesh_dir, f"obj_{obj_id_str}.ply")
+    if not os.path.exists(path):
+        return None
+    counts, body, rows, tris = {"vertex": 0, "face": 0}, False, [], []
+    n_face_lines = 0
+    with open(path, "r") as f:
+        for line in f:
+            v = line.split()
+            if not body:
+                if len(v) == 3 and v[0] == "element" and v[1] in counts:
+                    counts[v[1]] = int(v[2])
+                body = "end_header" in line
+                continue
+            if not v:
+                continue
+            if len(rows) < counts["vertex"]:
+                rows.append((float(v[0]), float(v[1]), float(v[2])))
+            elif n_face_lines < counts["face"]:
+                n_face_lines += 1
+                k = int(v[0])
+                idx = [int(x) for x in v[1:1 + k]]
+                tris.extend((idx[0], idx[j], idx[j + 1]) for j in range(1, len(idx) - 1))
+            else:
+                break
+    if not rows or not tris:
+        return None
+    verts = (np.array(rows, dtype=np.float64).reshape(-1, 3) / 1000.0).astype(np.float32)
+    faces = np.array(tris, dtype=np.int32).reshape(-1, 3)
+    diameter = _info_diameter(mesh_dir, obj_id_str)
     if diameter is None:
-        p = pts.astype(np.float64)
-        diameter = max(float(np.sqrt(((p[s:s + 256, None] - p[None]) ** 2).sum(-1).max()))
-                       for s in range(0, len(p), 256))
-    return pts, diameter
+        diameter = _largest_distance(verts)
+    return verts, faces, diameter
 
 
 def _host_boxes(boxes):
@@ -357,10 +415,10 @@ class PoseResult:
     valid = property(lambda s: s._valid[:s.n].bool())
 
     def cpu(self):
-        return PoseResult(self._buf.cpu(), self._bucket, self.n)
+        return type(self)(self._buf.cpu(), self._bucket, self.n)
 
     def clone(self):
-        return PoseResult(self._buf.clone(), self._bucket, self.n)
+        return type(self)(self._buf.clone(), self._bucket, self.n)
 
 
 RefineOutput = namedtuple("RefineOutput", "quat trans quat32 trans32 n_corr rms refined pose_trace corr samples")
@@ -475,24 +533,143 @@ class RefinedPoseResult(PoseResult):
     rms = property(lambda s: s._rms[:s.n])
     refined = property(lambda s: s._refined[:s.n].bool())
 
-    def cpu(self):
-        return RefinedPoseResult(self._buf.cpu(), self._bucket, self.n)
 
-    def clone(self):
-        return RefinedPoseResult(self._buf.clone(), self._bucket, self.n)
+VerifyOutput = namedtuple("VerifyOutput", "counts fit agree resid verified zbuf cls")
+
+
+class PoseVerifier:
+    """Render-and-compare verification of estimated poses against the depth frame, one
+    pose6d_pose_verify launch for N detections (DESIGN.md "Pose verification").
+
+    meshes: {key: (verts (V, 3) metres, faces (T, 3))}, diameters: {key: metres}
+    (load_mesh_triangles' results), the keys those of the estimator's `corners` dict; a face
+    index outside its mesh's vertices is refused here.  grid: samples per box side (G, P = G * G
+    per box, 1..64); tau: the tolerance as a fraction of the object's diameter.  The triangle
+    table is packed once per device.
+
+    __call__(depth, boxes, obj, quat, trans, frame_of=None, K=DEFAULT_K, maps=False, out=None),
+    all device tensors, as DepthRefiner takes them (obj: slots(keys), -1 = no mesh).  Returns a
+    VerifyOutput: counts (N, 5) i32 (no hit, hit without depth, consistent, occluded, violated),
+    fit (N,) f64 = consistent / (consistent + occluded + violated), agree (N,) f64 = consistent
+    / (consistent + violated), resid (N,) f64 mean |z_obs - z| of the consistent samples (m),
+    verified (N,) u8 and, with maps=True, zbuf (N, P) f64 (+inf: no hit) and cls (N, P) u8 (None
+    otherwise).  out: the five result tensors to write into (a captured graph's static
+    buffers).  choose=(base_fit (N,) f64, base_flag (N,) u8, best (N,) u8): the same launch
+    also writes best = base_flag & verified & (fit >= base_fit)."""
+
+    def __init__(self, meshes, diameters, grid=32, tau=0.1, depth_scale=0.001):
+        keys = [k for k, v in meshes.items() if v is not None]
+        missing = [k for k in keys if k not in diameters]
+        if missing:
+            raise Pose6dError(f"PoseVerifier: no diameter for {missing}")
+        self._slot = {k: i for i, k in enumerate(keys)}
+        self._verts = [np.array(meshes[k][0], np.float32).reshape(-1, 3) for k in keys]   # (copies)
+        self._faces = [np.array(meshes[k][1], np.int64).reshape(-1, 3) for k in keys]
+        for k, v, f in zip(keys, self._verts, self._faces):
+            if f.size and (f.min() < 0 or f.max() >= len(v)):
+                raise Pose6dError(f"PoseVerifier: mesh {k!r} has a face index outside [0, {len(v)})")
+        self._diam = [float(diameters[k]) for k in keys]
+        self.grid, self.tau, self.depth_scale = int(grid), float(tau), float(depth_scale)
+        self._tables = {}
+
+    def slots(self, keys):
+        """Triangle-table slots (int64 array) of a sequence of keys; -1 for a key without a mesh."""
+        return np.array([self._slot.get(k, -1) for k in keys], np.int64)
+
+    def table(self, dev):
+        """(verts, faces, voff, nverts, toff, ntri, diam, n_slots) on dev."""
+        T = self._tables.get(dev)
+        if T is None:
+            nv = np.array([len(v) for v in self._verts], np.int64)
+            nt = np.array([len(f) for f in self._faces], np.int64)
+            i32 = lambda a: torch.from_numpy(np.asarray(a).astype(np.int32)).to(dev)
+            cat = lambda parts, dt, w: np.concatenate(parts).astype(dt) if parts else np.zeros((0, w), dt)
+            T = self._tables[dev] = (
+                torch.from_numpy(cat(self._verts, np.float32, 3)).to(dev),
+                torch.from_numpy(cat(self._faces, np.int32, 3)).to(dev),
+                i32(np.cumsum(nv) - nv), i32(nv), i32(np.cumsum(nt) - nt), i32(nt),
+                torch.tensor(self._diam, dtype=torch.float64, device=dev), len(nv))
+        return T
+
+    def empty_outputs(self, N, dev):
+        e = lambda dt, *s: torch.empty(*s, device=dev, dtype=dt)
+        return (e(torch.int32, N, 5), e(torch.float64, N), e(torch.float64, N), e(torch.float64, N),
+                e(torch.uint8, N))
+
+    def __call__(self, depth, boxes, obj, quat, trans, frame_of=None, K=DEFAULT_K, maps=False, out=None, choose=None):
+        require_device(depth, boxes, obj, quat, trans, frame_of)
+        dev = quat.device
+        if depth.dim() == 2:
+            depth = depth[None]
+        if depth.dtype != torch.uint16 or depth.dim() != 3:
+            raise Pose6dError(f"PoseVerifier: depth must be (F, H, W) uint16, got {tuple(depth.shape)} {depth.dtype}")
+        F, H, W = depth.shape
+        N = quat.shape[0]
+        q = quat.detach().to(torch.float32).contiguous()
+        t = trans.detach().to(torch.float64).contiguous()
+        if q.shape != (N, 4) or t.shape != (N, 3) or obj.numel() != N or tuple(boxes.shape) != (N, 4):
+            raise Pose6dError("PoseVerifier: boxes (N, 4), obj (N,), quat (N, 4) and trans (N, 3) must agree")
+        fo = frame_of.to(torch.int32).contiguous() if frame_of is not None else None
+        if fo is not None and fo.numel() != N:
+            raise Pose6dError(f"PoseVerifier: frame_of must have one entry per box ({N}), got {fo.numel()}")
+        Kd, per_frame = K if isinstance(K, tuple) else _k_dev(K, dev)
+        if per_frame and Kd.shape[0] < F:
+            raise Pose6dError(f"PoseVerifier: per-frame K must have {F} rows, got {Kd.shape[0]}")
+        if out is None:
+            out = self.empty_outputs(N, dev)
+        P = self.grid * self.grid
+        dbg = (None, None)
+        if maps:
+            dbg = (torch.empty(N, P, device=dev, dtype=torch.float64),
+                   torch.empty(N, P, device=dev, dtype=torch.uint8))
+        if choose is not None and not (choose[0].dtype == torch.float64 and choose[1].dtype == torch.uint8
+                                       and choose[2].dtype == torch.uint8
+                                       and all(c.numel() == N and c.is_contiguous() for c in choose)):
+            raise Pose6dError("PoseVerifier: choose must be (base_fit f64, base_flag u8, best u8), N entries each")
+        call("pose_verify", depth.contiguous(), F, H, W, self.depth_scale, Kd, per_frame,
+             boxes.to(torch.int32).contiguous(), fo, obj.to(torch.int64).contiguous(), *self.table(dev), q, t, N,
+             self.grid, self.tau, *out, *dbg, *(choose or (None, None, None)), stream())
+        return VerifyOutput(*out, *dbg)
+
+
+_VERIFY_FIELDS = (("fit", torch.float64, ()), ("agree", torch.float64, ()), ("counts", torch.int32, (5,)),
+                  ("resid", torch.float64, ()), ("verified", torch.uint8, ()))
+
+
+@functools.lru_cache(maxsize=None)
+def _result_type(refined, verified):
+    """The result class of a PoseEstimator from its options: PoseResult, RefinedPoseResult, or
+    one of them extended by the verification's fields (PoseEstimator(verify=...)) -- fit, agree
+    (N,) f64, counts (N, 5) i32, resid (N,) f64, verified (N,) bool of the network's pose and,
+    with refine=, fit_ref ... verified_ref of the refined pose and best (N,) uint8: 1 where
+    refined, verified_ref and fit_ref >= fit all hold (use the refined pose).  The earlier
+    fields keep their places in the buffer."""
+    base = RefinedPoseResult if refined else PoseResult
+    if not verified:
+        return base
+    fields = _VERIFY_FIELDS
+    if refined:
+        fields = fields + tuple((n + "_ref", dt, sh) for n, dt, sh in _VERIFY_FIELDS) + (("best", torch.uint8, ()),)
+    ns = {"_FIELDS": base._FIELDS + fields, "__doc__": base.__doc__ + "\n\n" + _result_type.__doc__}
+    for name, _, _ in fields:
+        view = (lambda s, a="_" + name: getattr(s, a)[:s.n])
+        ns[name] = property((lambda s, v=view: v(s).bool()) if name.startswith("verified") else view)
+    return type("Verified" + base.__name__, (base,), ns)
 
 
 class _Bucket:
     """The static buffers and (graph=True) the captured graph of one (detections bucket,
     depth present) pair."""
 
-    def __init__(self, B, dev, cropper, result=PoseResult):
+    def __init__(self, B, dev, cropper, result=PoseResult, refine=False, verify=False):
         self.B = B
         self.boxes = torch.zeros(B, 4, dtype=torch.int32, device=dev)
         self.frame_of = torch.zeros(B, dtype=torch.int32, device=dev)
         self.obj = torch.zeros(B, dtype=torch.int64, device=dev)
-        if result is not PoseResult:   # the refiner's mesh-table slots
+        if refine:   # the refiner's mesh-table slots
             self.obj_ref = torch.zeros(B, dtype=torch.int64, device=dev)
+        if verify:   # the verifier's triangle-table slots
+            self.obj_ver = torch.zeros(B, dtype=torch.int64, device=dev)
         self.crops = cropper.empty_outputs(B, dev)
         self.out = torch.zeros(result.nbytes(B), dtype=torch.uint8, device=dev)
         self.res = result(self.out, B, B)
@@ -530,10 +707,15 @@ class PoseEstimator:
     -> forward -> projection -> refinement of (quat, trans_cam) against the depth frame ->
     projection of the refined pose, all in the same graph, and the result is a
     RefinedPoseResult; a call without depth raises.  None: nothing changes.
+    verify: a PoseVerifier (keyed like `corners`) or None.  With one, a render-and-compare
+    launch on (quat, trans_cam) joins the graph and the result gains fit, agree, counts, resid
+    and verified; with refine= as well, a second launch on the refined pose adds fit_ref ...
+    verified_ref and best (1: use the refined pose); the result's class is _result_type's.  A
+    call without depth raises.  None: nothing is allocated or launched differently.
     """
 
     def __init__(self, model, corners, K=DEFAULT_K, class_to_obj=None, max_detections=32, max_frames=1, graph=True,
-                 dataset_intrinsics=False, img_size=224, bgr=False, axis_scale=0.1, refine=None):
+                 dataset_intrinsics=False, img_size=224, bgr=False, axis_scale=0.1, refine=None, verify=None):
         kind = type(model).__name__
         if kind not in _KINDS:
             raise Pose6dError(f"PoseEstimator: model must be one of {sorted(_KINDS)}, got {kind}")
@@ -553,8 +735,10 @@ class PoseEstimator:
         self.axis_scale = float(axis_scale)
         if refine is not None and not isinstance(refine, DepthRefiner):
             raise Pose6dError("PoseEstimator: refine must be a DepthRefiner or None")
-        self.refine = refine
-        self._result = PoseResult if refine is None else RefinedPoseResult
+        if verify is not None and not isinstance(verify, PoseVerifier):
+            raise Pose6dError("PoseEstimator: verify must be a PoseVerifier or None")
+        self.refine, self.verify = refine, verify
+        self._result = _result_type(refine is not None, verify is not None)
         self.cropper = CropDetections(img_size, True, bgr, dataset_intrinsics)
         if isinstance(corners, dict):
             keys = [k for k, v in corners.items() if v is not None]
@@ -613,10 +797,10 @@ class PoseEstimator:
             rows[i] = self._row.get(key, -1)
         return rows
 
-    def _ref_objs(self, classes):
-        """The refiner's mesh-table slot of every detection (-1: no mesh, passed through)."""
+    def _slots(self, engine, classes):
+        """The refiner's or the verifier's table slot of every detection (-1: no mesh)."""
         c = np.asarray(classes.cpu().numpy() if isinstance(classes, torch.Tensor) else classes).reshape(-1)
-        return self.refine.slots([k if self.class_to_obj is None else self.class_to_obj.get(k) for k in c.tolist()])
+        return engine.slots([k if self.class_to_obj is None else self.class_to_obj.get(k) for k in c.tolist()])
 
     def _stage_frames(self, rgb, depth):
         dev = self.device
@@ -666,6 +850,15 @@ class PoseEstimator:
             pose_project(res._quat32_ref, res._trans32_ref, self._K, bk.obj, self.corners, boxes=None,
                          frame_of=bk.frame_of, axis_scale=self.axis_scale,
                          out=(None, res._points_ref, res._pixels_ref, None))
+        if self.verify is not None:
+            # render-and-compare of the network's pose and, with refine=, of the refined one: one
+            # launch each, the second also writing the choice between the two
+            self.verify(self._depth, bk.boxes, bk.obj_ver, res._quat, res._trans_cam, frame_of=bk.frame_of, K=self._K,
+                        out=(res._counts, res._fit, res._agree, res._resid, res._verified))
+            if self.refine is not None:
+                self.verify(self._depth, bk.boxes, bk.obj_ver, res._quat32_ref, res._trans_ref, frame_of=bk.frame_of,
+                            K=self._K, out=(res._counts_ref, res._fit_ref, res._agree_ref, res._resid_ref,
+                                            res._verified_ref), choose=(res._fit, res._refined, res._best))
 
     def __call__(self, rgb, depth, boxes, classes, frame_of=None):
         if self.model.training:
@@ -676,19 +869,23 @@ class PoseEstimator:
             raise Pose6dError(f"PoseEstimator: {N} detections, max_detections = {self.max_detections}")
         if self.refine is not None and depth is None:
             raise Pose6dError("PoseEstimator: refine= needs the depth frame (depth=None given)")
+        if self.verify is not None and depth is None:
+            raise Pose6dError("PoseEstimator: verify= needs the depth frame (depth=None given)")
         if N == 0:
             return self._result(torch.zeros(self._result.nbytes(1), dtype=torch.uint8, device=self.device), 1, 0)
         B = next(b for b in BUCKETS if b >= N)
         rgb_frames = rgb.shape[0] if rgb.ndim == 4 else 1
         fo = np.zeros(N, np.int64) if frame_of is None else _host_frame_of(frame_of, N, rgb_frames)
         rows = self._objs(classes, N)
-        ref_rows = self._ref_objs(classes) if self.refine is not None else None
+        ref_rows = self._slots(self.refine, classes) if self.refine is not None else None
+        ver_rows = self._slots(self.verify, classes) if self.verify is not None else None
         F = self._stage_frames(rgb, depth)
         assert F == rgb_frames
         has_depth = depth is not None
         bk = self._buckets.get((B, has_depth))
         if bk is None:
-            bk = self._buckets[(B, has_depth)] = _Bucket(B, self.device, self.cropper, self._result)
+            bk = self._buckets[(B, has_depth)] = _Bucket(B, self.device, self.cropper, self._result,
+                                                         self.refine is not None, self.verify is not None)
         # pad by repeating detection 0; one small host -> device copy per table
         pad = lambda a: np.concatenate([a, np.repeat(a[:1], B - N, axis=0)]) if B > N else a
         bk.boxes.copy_(torch.from_numpy(pad(bx).astype(np.int32)), non_blocking=True)
@@ -696,6 +893,8 @@ class PoseEstimator:
         bk.obj.copy_(torch.from_numpy(pad(rows)), non_blocking=True)
         if ref_rows is not None:
             bk.obj_ref.copy_(torch.from_numpy(pad(ref_rows)), non_blocking=True)
+        if ver_rows is not None:
+            bk.obj_ver.copy_(torch.from_numpy(pad(ver_rows)), non_blocking=True)
         own, self.model._p6_engines = self.model._p6_engines, bk.engines
         try:
             with torch.no_grad():

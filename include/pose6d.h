@@ -459,6 +459,56 @@ int pose6d_depth_refine(const uint16_t *depth, int32_t F, int32_t H, int32_t W, 
                         float *quat32_out, float *trans32_out, int32_t *n_corr, double *rms, uint8_t *refined,
                         double *pose_trace, int32_t *corr_out, double *samples_out, void *stream);
 
+/* ----------------------------------------------------------------------
+ * Pose verification: render-and-compare of N poses against the depth frame, ONE launch,
+ * one workgroup per detection.  The object's triangle mesh is rendered at the pose into a
+ * G x G z-buffer over the detection box and every sample is compared with the observed
+ * depth.  The reference project has no such step; the arithmetic contract below is
+ * restated in fp64 numpy by tests/verify_ref.py.  Everything is double, every product
+ * rounded on its own.
+ * depth, depth_scale, K, K_per_frame, boxes_xyxy, frame_of, F, obj: as
+ * pose6d_depth_refine; obj [N] int64 are slots of the packed TRIANGLE table: verts float
+ * [sum V][3] metres, faces int32 [sum T][3] (indices local to the object), voff / nverts /
+ * toff / ntri int32 [n_slots] (first vertex, vertex count, first triangle, triangle
+ * count), diam double [n_slots].  quat [N][4] fp32 (x, y, z, w), normalised in double as
+ * pose6d_depth_refine does; trans [N][3] double.
+ * Vertices: c = R m + t, each row summed left to right; pu = c.x * fx / c.z + cx, pv
+ * alike.  A triangle is skipped when an index is outside [0, nverts) (never
+ * dereferenced), a vertex has c.z <= 0.001 or a projected coordinate is not finite.
+ * Samples: pose6d_depth_refine's G x G grid, sample k = j * G + i at the integer pixel p.
+ * Coverage: e(a, b, p) = (b.u - a.u)(p.v - a.v) - (b.v - a.v)(p.u - a.u); w0 = e(v1, v2,
+ * p), w1 = e(v2, v0, p), w2 = e(v0, v1, p), s = (w0 + w1) + w2; covered when all three w
+ * >= 0 and s > 0, or all three <= 0 and s < 0 (both windings, inclusive edges, no
+ * back-face culling), and p lies inside the triangle's pixel bounding box -- implied in
+ * exact arithmetic, stated so that culling by the box is exact in floating point.  The
+ * rendered depth is z = s / ((w0 / z0 + w1 / z1) + w2 / z2), kept when positive and
+ * finite; the z-buffer holds the minimum per sample.  The result is DEFINED by every
+ * triangle against every sample; the kernel only skips what the box test excludes.
+ * Classes, from d = depth[v][u] (0 outside the frame) and z_obs = d * depth_scale: 0 no
+ * hit; 1 hit, d == 0; 2 consistent, |z_obs - z| <= tau * diam; 3 occluded, z_obs - z <
+ * -tau * diam; 4 violated, z_obs - z > tau * diam.
+ * Outputs: counts [N][5] int32; fit [N] double = n2 / (n2 + n3 + n4); agree [N] double =
+ * n2 / (n2 + n4) (both 0 on a zero denominator); resid [N] double, the mean |z_obs - z|
+ * over class 2 (0 without one), summed in a fixed order; verified [N] uint8.  verified =
+ * 0 with zeros elsewhere: obj outside the table or a slot without triangles, a zero / NaN
+ * / infinite quaternion, frame_of outside [0, F).
+ * Optional, NULL in the product path: zbuf_out [N][P] double (+inf: no hit) and cls_out
+ * [N][P] uint8 (P = G * G); a detection with verified = 0 has +inf and 0 there.
+ * Optional choice between two poses of the same detections (best needs both others):
+ * best [N] uint8 = base_flag[n] != 0 && verified && fit >= base_fit[n], with base_fit [N]
+ * double the fit of an earlier launch and base_flag [N] uint8 a condition on this pose
+ * (the refiner's `refined`).
+ * G in [1, 64], tau > 0 (a fraction of the diameter), depth_scale > 0, N, F, H, W >= 0.
+ * ---------------------------------------------------------------------- */
+int pose6d_pose_verify(const uint16_t *depth, int32_t F, int32_t H, int32_t W, double depth_scale, const double *K,
+                       int32_t K_per_frame, const int32_t *boxes_xyxy, const int32_t *frame_of, const int64_t *obj,
+                       const float *verts, const int32_t *faces, const int32_t *voff, const int32_t *nverts,
+                       const int32_t *toff, const int32_t *ntri, const double *diam, int32_t n_slots,
+                       const float *quat, const double *trans, int32_t N, int32_t G, double tau, int32_t *counts,
+                       double *fit, double *agree, double *resid, uint8_t *verified, double *zbuf_out,
+                       uint8_t *cls_out, const double *base_fit, const uint8_t *base_flag, uint8_t *best,
+                       void *stream);
+
 /* ------------------------------------------------------------------------
  * ResNet50 trunk — replaces torchvision.models.resnet50 children[:-1] as
  * wrapped by every model (pose_net_rgb.py:18-20, pose_net_rgb_geometric.py:18-20,

@@ -17,6 +17,11 @@ projected box corners, the 4 axis points (origin, x, y, z) and `valid` (false: n
 point-to-point ICP on --refine-points mesh points for --refine-iters iterations) and adds
 per detection `quat_ref_xyzw`, `trans_ref_m`, `box2d_ref`, `axes2d_ref`, `n_corr`, `rms_m`
 (first and last iteration) and `refined`; without the flag the output is unchanged.
+--verify (needs --depth) renders every object's triangle mesh at its pose and compares it with
+the depth frame (pose6d.infer.PoseVerifier, tolerance --verify-tau of the diameter) and adds
+per detection `fit`, `agree`, `counts` (no hit, no depth, consistent, occluded, violated),
+`resid_m` and `verified`; with --refine also their `_ref` forms for the refined pose and
+`best` (true: use the refined pose).
 """
 import argparse
 import json
@@ -49,8 +54,11 @@ def main(argv=None):
     ap.add_argument("--refine", action="store_true", help="refine the poses against the depth frame (ICP)")
     ap.add_argument("--refine-iters", type=int, default=10)
     ap.add_argument("--refine-points", type=int, default=1500, help="mesh points per object")
+    ap.add_argument("--verify", action="store_true", help="render-and-compare every pose against the depth frame")
+    ap.add_argument("--verify-tau", type=float, default=0.1, help="depth tolerance, a fraction of the diameter")
     a = ap.parse_args(argv)
-    from pose6d.infer import DEFAULT_K, DepthRefiner, PoseEstimator, load_mesh_corners, load_mesh_points
+    from pose6d.infer import (DEFAULT_K, DepthRefiner, PoseEstimator, PoseVerifier, load_mesh_corners, load_mesh_points,
+                              load_mesh_triangles)
     from pose6d.linemod import load_depth, load_rgb
     from tools.compare_models import load_model
 
@@ -60,6 +68,9 @@ def main(argv=None):
     depth = load_depth(a.depth, rgb.shape[:2]) if a.depth else None
     if a.refine and depth is None:
         print("Error: --refine needs --depth", file=sys.stderr)
+        return 1
+    if a.verify and depth is None:
+        print("Error: --verify needs --depth", file=sys.stderr)
         return 1
     if a.model in ("RGBD", "RGBD-Geometric") and depth is None:
         print("Warning: no depth image, using zeros", file=sys.stderr)
@@ -78,8 +89,13 @@ def main(argv=None):
         meshes = {k: v for k, v in meshes.items() if v is not None}
         refine = DepthRefiner({k: v[0] for k, v in meshes.items()}, {k: v[1] for k, v in meshes.items()},
                               iters=a.refine_iters)
+    verify = None
+    if a.verify:
+        tri = {name: load_mesh_triangles(a.mesh_dir, name) for name in corners}
+        tri = {k: v for k, v in tri.items() if v is not None}
+        verify = PoseVerifier({k: v[:2] for k, v in tri.items()}, {k: v[2] for k, v in tri.items()}, tau=a.verify_tau)
     est = PoseEstimator(model, corners, K=DEFAULT_K, max_detections=32, graph=False,
-                        dataset_intrinsics=a.dataset_intrinsics, refine=refine)
+                        dataset_intrinsics=a.dataset_intrinsics, refine=refine, verify=verify)
     out = []
     for s in range(0, len(dets), 32):   # the scripts have no limit; the estimator takes 32 at a time
         part = dets[s:s + 32]
@@ -94,6 +110,14 @@ def main(argv=None):
                                 "box2d_ref": res.box2d_ref[i].tolist(), "axes2d_ref": res.axes2d_ref[i].tolist(),
                                 "n_corr": int(res.n_corr[i]), "rms_m": res.rms[i].tolist(),
                                 "refined": bool(res.refined[i])})
+            if a.verify:
+                for sfx in ("", "_ref") if a.refine else ("",):
+                    get = lambda name: getattr(res, name + sfx)[i]
+                    out[-1].update({"fit" + sfx: float(get("fit")), "agree" + sfx: float(get("agree")),
+                                    "counts" + sfx: get("counts").tolist(), "resid_m" + sfx: float(get("resid")),
+                                    "verified" + sfx: bool(get("verified"))})
+                if a.refine:
+                    out[-1]["best"] = bool(res.best[i])
     est.check()
     text = json.dumps({"image": a.image, "model": a.model, "poses": out}, indent=1)
     if a.out:
