@@ -7,9 +7,7 @@
 // (detection, point); 12 points: the 8 box corners, the origin, the x / y / z axis tips
 // at axis_scale.  Built with -ffp-contract=off: each product and sum rounds on its own,
 // as numpy's do (numpy's 3-term matmul may still order or fuse its products differently).
-#include <math.h>
-
-#include "common.h"
+#include "pose_geom.h"
 
 namespace {
 
@@ -34,9 +32,8 @@ __global__ __launch_bounds__(kThreads) void pose_project_kernel(
   const int f = (K_per_frame && frame_of) ? frame_of[i] : 0;
   const int64_t ob = obj[i];
   // scipy Rotation.from_quat: float64, q / sqrt(x^2 + y^2 + z^2 + w^2)
-  double x = (double)quat[4 * i], y = (double)quat[4 * i + 1], z = (double)quat[4 * i + 2],
-         w = (double)quat[4 * i + 3];
-  const double nrm = sqrt(x * x + y * y + z * z + w * w);
+  double q[4];
+  const double nrm = p6::quat_load(quat + 4 * i, q);
   const bool ok = ob >= 0 && ob < n_obj && nrm > 0.0 && f >= 0 && f < F;
   if (!ok) {   // nothing is read through the bad index
     if (p == 0) {
@@ -60,13 +57,9 @@ __global__ __launch_bounds__(kThreads) void pose_project_kernel(
     if (valid_out) valid_out[i] = 1;
     if (trans_out) { trans_out[3 * i] = tx; trans_out[3 * i + 1] = ty; trans_out[3 * i + 2] = tz; }
   }
-  x /= nrm; y /= nrm; z /= nrm; w /= nrm;
-  // Rotation.as_matrix
-  const double x2 = x * x, y2 = y * y, z2 = z * z, w2 = w * w;
-  const double xy = x * y, zw = z * w, xz = x * z, yw = y * w, yz = y * z, xw = x * w;
-  const double r00 = x2 - y2 - z2 + w2, r01 = 2.0 * (xy - zw), r02 = 2.0 * (xz + yw);
-  const double r10 = 2.0 * (xy + zw), r11 = -x2 + y2 - z2 + w2, r12 = 2.0 * (yz - xw);
-  const double r20 = 2.0 * (xz - yw), r21 = 2.0 * (yz + xw), r22 = -x2 - y2 + z2 + w2;
+  double R[9];
+  p6::quat_unit(q, nrm);   // (the sign it may flip cancels in every entry of R)
+  p6::quat_to_mat(q, R);
   double c0 = 0.0, c1 = 0.0, c2 = 0.0;
   if (p < 8) {
     const double* c = corners + (ob * 8 + p) * 3;
@@ -79,9 +72,9 @@ __global__ __launch_bounds__(kThreads) void pose_project_kernel(
     c2 = axis_scale;
   }
   // project_points (visualization.py:26-31)
-  const double px = r00 * c0 + r01 * c1 + r02 * c2 + tx;
-  const double py = r10 * c0 + r11 * c1 + r12 * c2 + ty;
-  const double pz = r20 * c0 + r21 * c1 + r22 * c2 + tz;
+  const double px = R[0] * c0 + R[1] * c1 + R[2] * c2 + tx;
+  const double py = R[3] * c0 + R[4] * c1 + R[5] * c2 + ty;
+  const double pz = R[6] * c0 + R[7] * c1 + R[8] * c2 + tz;
   const double zc = pz < 0.001 ? 0.001 : pz;   // np.clip(z, 0.001, None); a NaN stays a NaN
   const double u = px * k[0] / zc + k[2];
   const double v = py * k[4] / zc + k[5];

@@ -26,9 +26,7 @@
 // Built with -ffp-contract=off: the back-projection and the gate round product by
 // product, as numpy does, so the kept set equals the restatement's bit for bit; the
 // only fused operations are the explicit fmaf calls of the squared distance.
-#include <math.h>
-
-#include "common.h"
+#include "pose_geom.h"
 
 namespace {
 
@@ -37,21 +35,6 @@ constexpr int kMaxWaves = 16;    // 1024 lanes
 constexpr int kMom = 17;         // n, sum p' [3], sum m [3], sum m p'^T [9], sum s
 constexpr int kSweeps = 6;       // cyclic Jacobi sweeps on the 4 x 4 (quadratic convergence: 4 leave
                                  // 6e-8 rad, 5 reach fp64 roundoff on random pair sets; one is margin)
-
-__device__ __forceinline__ int64_t floor_div(int64_t a, int64_t b) {   // b > 0
-  const int64_t q = a / b;
-  return (a % b != 0 && a < 0) ? q - 1 : q;
-}
-
-// unit quaternion (x, y, z, w) -> rotation matrix, row-major
-__device__ __forceinline__ void quat_to_mat(const double* q, double* R) {
-  const double x = q[0], y = q[1], z = q[2], w = q[3];
-  const double x2 = x * x, y2 = y * y, z2 = z * z, w2 = w * w;
-  const double xy = x * y, zw = z * w, xz = x * z, yw = y * w, yz = y * z, xw = x * w;
-  R[0] = x2 - y2 - z2 + w2; R[1] = 2.0 * (xy - zw);    R[2] = 2.0 * (xz + yw);
-  R[3] = 2.0 * (xy + zw);   R[4] = -x2 + y2 - z2 + w2; R[5] = 2.0 * (yz - xw);
-  R[6] = 2.0 * (xz - yw);   R[7] = 2.0 * (yz + xw);    R[8] = -x2 - y2 + z2 + w2;
-}
 
 // one Jacobi rotation of the symmetric A (and the eigenvector matrix V) in the (P, Q) plane
 template <int P, int Q>
@@ -116,10 +99,7 @@ __device__ void horn_quat(const double* S, double* q) {
   q[0] = sg * e[1] / nrm; q[1] = sg * e[2] / nrm; q[2] = sg * e[3] / nrm; q[3] = sg * e[0] / nrm;
 }
 
-struct RefineArgs {
-  const uint16_t* depth; int F, H, W; double depth_scale;
-  const double* K; int K_per_frame;
-  const int32_t* boxes; const int32_t* frame_of; const int64_t* obj;
+struct RefineArgs : p6::FrameArgs {
   const float* points; const int32_t* off; const int32_t* npts; const double* diam; int n_slots;
   const float* quat; const double* trans;
   int G, iters; double gate, trim; int min_points;
@@ -138,22 +118,11 @@ __global__ __launch_bounds__(1024) void depth_refine_kernel(const RefineArgs a) 
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
   const int G = a.G, P = G * G, iters = a.iters;
 
-  // ---- the detection's header: every thread reads the same words, so every branch on
-  // them is uniform
-  const int64_t ob = a.obj[b];
-  const int f = a.frame_of ? a.frame_of[b] : 0;
-  const int n = (ob >= 0 && ob < a.n_slots) ? a.npts[ob] : 0;
-  double q0[4] = {(double)a.quat[4 * b], (double)a.quat[4 * b + 1], (double)a.quat[4 * b + 2],
-                  (double)a.quat[4 * b + 3]};
+  const p6::Detection det = p6::read_detection(a, a.n_slots, a.npts, a.quat, b);
+  const int64_t ob = det.ob;
+  const double* q0 = det.q;
   const double t0[3] = {a.trans[3 * b], a.trans[3 * b + 1], a.trans[3 * b + 2]};
-  const double qn = sqrt(q0[0] * q0[0] + q0[1] * q0[1] + q0[2] * q0[2] + q0[3] * q0[3]);
-  const bool q_ok = qn > 0.0 && qn < __builtin_inf();   // false for a zero, NaN or infinite quaternion
-  if (q_ok) {
-    const double sg = q0[3] < 0.0 ? -1.0 : 1.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) q0[k] = sg * q0[k] / qn;
-  }
-  const bool ok = q_ok && n > 0 && f >= 0 && f < a.F;
+  const int n = det.n;
 
   // the final outputs (thread 0) and the rest of the debug rows
   auto finish = [&](int done, const double* q, const double* t, int nc, double rms0, double rms1, int ref) {
@@ -190,7 +159,7 @@ __global__ __launch_bounds__(1024) void depth_refine_kernel(const RefineArgs a) 
     for (int k = 0; k < 3; ++k) row[4 + k] = t[k];
   };
 
-  if (!ok) {   // nothing is read through the bad index
+  if (!det.ok) {   // nothing is read through the bad index
     if (tid == 0) trace_row(0, q0, t0);
     if (a.samples_out && tid < P)
       for (int k = 0; k < 3; ++k) a.samples_out[((int64_t)b * P + tid) * 3 + k] = __builtin_nan("");
@@ -204,22 +173,17 @@ __global__ __launch_bounds__(1024) void depth_refine_kernel(const RefineArgs a) 
   bool kept = false;
   double pc[3] = {0.0, 0.0, 0.0};   // the sample relative to the initial translation
   if (tid < P) {
-    const int32_t* bx = a.boxes + 4 * b;
-    const int i = tid % G, j = tid / G;
-    const int64_t u = (int64_t)bx[0] + floor_div((int64_t)(2 * i + 1) * ((int64_t)bx[2] - (int64_t)bx[0]), 2 * G);
-    const int64_t v = (int64_t)bx[1] + floor_div((int64_t)(2 * j + 1) * ((int64_t)bx[3] - (int64_t)bx[1]), 2 * G);
+    const int64_t u = p6::sample_pixel(det.box[0], det.box[2], tid % G, G);
+    const int64_t v = p6::sample_pixel(det.box[1], det.box[3], tid / G, G);
     double p[3] = {__builtin_nan(""), __builtin_nan(""), __builtin_nan("")};
-    if (u >= 0 && u < a.W && v >= 0 && v < a.H) {
-      const uint16_t d = a.depth[((int64_t)f * a.H + v) * a.W + u];
-      if (d > 0) {
-        const double* k = a.K + ((a.K_per_frame && a.frame_of) ? 9 * (int64_t)f : 0);
-        const double z = (double)d * a.depth_scale;
-        const double x = ((double)u - k[2]) * z / k[0];
-        const double y = ((double)v - k[5]) * z / k[4];
-        const double dx = x - t0[0], dy = y - t0[1], dz = z - t0[2];
-        kept = sqrt(dx * dx + dy * dy + dz * dz) <= gate_r;
-        if (kept) { p[0] = x; p[1] = y; p[2] = z; pc[0] = dx; pc[1] = dy; pc[2] = dz; }
-      }
+    const uint16_t d = p6::depth_at(a, det.f, u, v);
+    if (d > 0) {
+      const double z = (double)d * a.depth_scale;
+      const double x = ((double)u - det.k[2]) * z / det.k[0];
+      const double y = ((double)v - det.k[5]) * z / det.k[4];
+      const double dx = x - t0[0], dy = y - t0[1], dz = z - t0[2];
+      kept = sqrt(dx * dx + dy * dy + dz * dz) <= gate_r;
+      if (kept) { p[0] = x; p[1] = y; p[2] = z; pc[0] = dx; pc[1] = dy; pc[2] = dz; }
     }
     if (a.samples_out)
       for (int k = 0; k < 3; ++k) a.samples_out[((int64_t)b * P + tid) * 3 + k] = p[k];
@@ -240,7 +204,7 @@ __global__ __launch_bounds__(1024) void depth_refine_kernel(const RefineArgs a) 
   const bool one_tile = n <= kTile;
   if (one_tile) stage(0);
   if (tid == 0) {
-    quat_to_mat(q0, pose_s);
+    p6::quat_to_mat(q0, pose_s);
     for (int k = 0; k < 3; ++k) pose_s[9 + k] = t0[k];
     for (int k = 0; k < 4; ++k) pose_s[12 + k] = q0[k];
     trace_row(0, q0, t0);
@@ -332,7 +296,7 @@ __global__ __launch_bounds__(1024) void depth_refine_kernel(const RefineArgs a) 
           for (int c = 0; c < 3; ++c) S[3 * r + c] = T[7 + 3 * r + c] - T[0] * mb[r] * pb[c];
         double qn4[4], Rn[9], tn[3];
         horn_quat(S, qn4);
-        quat_to_mat(qn4, Rn);
+        p6::quat_to_mat(qn4, Rn);
         for (int r = 0; r < 3; ++r)
           tn[r] = t0[r] + (pb[r] - (Rn[3 * r] * mb[0] + Rn[3 * r + 1] * mb[1] + Rn[3 * r + 2] * mb[2]));
         for (int k = 0; k < 9; ++k) pose_s[k] = Rn[k];
@@ -385,7 +349,7 @@ extern "C" int pose6d_depth_refine(const uint16_t* depth, int32_t F, int32_t H, 
   P6_CHECK_ARG(depth && K && boxes_xyxy && obj && quat && trans, "pose6d_depth_refine: null input");
   P6_CHECK_ARG(n_slots == 0 || (points && off && npts && diam), "pose6d_depth_refine: null mesh table");
   P6_CHECK_ARG(quat_out && trans_out && n_corr && rms && refined, "pose6d_depth_refine: null output");
-  const RefineArgs a = {depth, F, H, W, depth_scale, K, K_per_frame, boxes_xyxy, frame_of, obj, points, off, npts,
+  const RefineArgs a = {{depth, F, H, W, depth_scale, K, K_per_frame, boxes_xyxy, frame_of, obj}, points, off, npts,
                         diam, n_slots, quat, trans, G, iters, gate, trim, min_points, quat_out, trans_out,
                         quat32_out, trans32_out, n_corr, rms, refined, pose_trace, corr_out, samples_out};
   const int threads = (G * G + 63) & ~63;

@@ -5,8 +5,7 @@
 // tests/verify_ref.py, which tests every triangle against every sample.
 //
 // One workgroup of 1024 lanes per detection.  Per detection:
-//   samples   the refiner's grid: pixel u_i = x1 + floor((2i + 1)(x2 - x1) / 2G), v_j alike,
-//             G doubles each in LDS;
+//   samples   the refiner's grid (pose_geom.h sample_pixel), G doubles per axis in LDS;
 //   render    lanes stride over the triangles.  A lane projects its triangle's three
 //             vertices in double (c = R m + t row by row, left to right; pu = c.x * fx / c.z
 //             + cx), maps the triangle's pixel bounding box to a range of sample columns and
@@ -27,9 +26,7 @@
 //
 // Built with -ffp-contract=off: every product rounds on its own, as numpy's do, so the
 // z-buffer equals the restatement's bit for bit.  Plain C++ only.
-#include <math.h>
-
-#include "common.h"
+#include "pose_geom.h"
 
 namespace {
 
@@ -37,21 +34,6 @@ constexpr int kThreads = 1024;
 constexpr int kWaves = kThreads / 64;
 constexpr int kMaxG = 64;
 constexpr unsigned long long kNoHit = ~0ull;
-
-__device__ __forceinline__ int64_t floor_div(int64_t a, int64_t b) {   // b > 0
-  const int64_t q = a / b;
-  return (a % b != 0 && a < 0) ? q - 1 : q;
-}
-
-// unit quaternion (x, y, z, w) -> rotation matrix, row-major (refine.hip's)
-__device__ __forceinline__ void quat_to_mat(const double* q, double* R) {
-  const double x = q[0], y = q[1], z = q[2], w = q[3];
-  const double x2 = x * x, y2 = y * y, z2 = z * z, w2 = w * w;
-  const double xy = x * y, zw = z * w, xz = x * z, yw = y * w, yz = y * z, xw = x * w;
-  R[0] = x2 - y2 - z2 + w2; R[1] = 2.0 * (xy - zw);    R[2] = 2.0 * (xz + yw);
-  R[3] = 2.0 * (xy + zw);   R[4] = -x2 + y2 - z2 + w2; R[5] = 2.0 * (yz - xw);
-  R[6] = 2.0 * (xz - yw);   R[7] = 2.0 * (yz + xw);    R[8] = -x2 - y2 + z2 + w2;
-}
 
 // A superset of the sample indices i in [0, G) whose pixel x1 + floor((2i + 1) w / 2G) lies in
 // [lo, hi] (finite), for w = x2 - x1 > 0.  With r_i = (2i + 1) w / 2G the pixel is in (x1 + r_i
@@ -77,10 +59,7 @@ __device__ __forceinline__ void sample_range(double lo, double hi, int x1, int x
   i1 = (int)fmax(fmin(b, (double)(G - 1)), -1.0);   // -1: an empty range
 }
 
-struct VerifyArgs {
-  const uint16_t* depth; int F, H, W; double depth_scale;
-  const double* K; int K_per_frame;
-  const int32_t* boxes; const int32_t* frame_of; const int64_t* obj;
+struct VerifyArgs : p6::FrameArgs {
   const float* verts; const int32_t* faces; const int32_t* voff; const int32_t* nverts; const int32_t* toff;
   const int32_t* ntri; const double* diam; int n_slots;
   const float* quat; const double* trans;
@@ -98,16 +77,10 @@ __global__ __launch_bounds__(kThreads) void pose_verify_kernel(const VerifyArgs 
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int G = a.G, P = G * G;
 
-  // ---- the detection's header: every thread reads the same words, so every branch on them
-  // is uniform
-  const int64_t ob = a.obj[b];
-  const int f = a.frame_of ? a.frame_of[b] : 0;
-  const int nt = (ob >= 0 && ob < a.n_slots) ? a.ntri[ob] : 0;
-  double q[4] = {(double)a.quat[4 * b], (double)a.quat[4 * b + 1], (double)a.quat[4 * b + 2],
-                 (double)a.quat[4 * b + 3]};
-  const double qn = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  const bool ok = qn > 0.0 && qn < __builtin_inf() && nt > 0 && f >= 0 && f < a.F;
-  if (!ok) {   // nothing is read through the bad index
+  const p6::Detection det = p6::read_detection(a, a.n_slots, a.ntri, a.quat, b);
+  const int64_t ob = det.ob;
+  const int nt = det.n;
+  if (!det.ok) {   // nothing is read through the bad index
     if (tid == 0) {
       for (int k = 0; k < 5; ++k) a.counts[5 * b + k] = 0;
       a.fit[b] = a.agree[b] = a.resid[b] = 0.0;
@@ -120,21 +93,16 @@ __global__ __launch_bounds__(kThreads) void pose_verify_kernel(const VerifyArgs 
     }
     return;
   }
-  const double sg = q[3] < 0.0 ? -1.0 : 1.0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) q[k] = sg * q[k] / qn;
   double R[9];
-  quat_to_mat(q, R);
+  p6::quat_to_mat(det.q, R);
   const double t[3] = {a.trans[3 * b], a.trans[3 * b + 1], a.trans[3 * b + 2]};
-  const double* kk = a.K + ((a.K_per_frame && a.frame_of) ? 9 * (int64_t)f : 0);
-  const double fx = kk[0], cx = kk[2], fy = kk[4], cy = kk[5];
-  const int32_t* bx = a.boxes + 4 * b;
-  const int x1 = bx[0], y1 = bx[1], x2 = bx[2], y2 = bx[3];
+  const double fx = det.k[0], cx = det.k[2], fy = det.k[4], cy = det.k[5];
+  const int x1 = det.box[0], y1 = det.box[1], x2 = det.box[2], y2 = det.box[3];
 
   // ---- samples and an empty z-buffer
   if (tid < G) {
-    us[tid] = (double)((int64_t)x1 + floor_div((int64_t)(2 * tid + 1) * ((int64_t)x2 - (int64_t)x1), 2 * G));
-    vs[tid] = (double)((int64_t)y1 + floor_div((int64_t)(2 * tid + 1) * ((int64_t)y2 - (int64_t)y1), 2 * G));
+    us[tid] = (double)p6::sample_pixel(x1, x2, tid, G);   // exact: below 2^33
+    vs[tid] = (double)p6::sample_pixel(y1, y2, tid, G);
   }
   for (int k = tid; k < P; k += kThreads) zb[k] = kNoHit;
   __syncthreads();
@@ -217,10 +185,7 @@ __global__ __launch_bounds__(kThreads) void pose_verify_kernel(const VerifyArgs 
     const double z = hit ? __longlong_as_double((long long)bits) : __builtin_inf();
     int cls = 0;
     if (hit) {
-      const double su = us[k % G], sv = vs[k / G];
-      uint16_t d = 0;
-      if (su >= 0.0 && su < (double)a.W && sv >= 0.0 && sv < (double)a.H)
-        d = a.depth[((int64_t)f * a.H + (int64_t)sv) * a.W + (int64_t)su];
+      const uint16_t d = p6::depth_at(a, det.f, (int64_t)us[k % G], (int64_t)vs[k / G]);
       if (d == 0) {
         cls = 1;
       } else {
@@ -282,7 +247,7 @@ extern "C" int pose6d_pose_verify(const uint16_t* depth, int32_t F, int32_t H, i
                "pose6d_pose_verify: null triangle table");
   P6_CHECK_ARG(counts && fit && agree && resid && verified, "pose6d_pose_verify: null output");
   P6_CHECK_ARG(!best || (base_fit && base_flag), "pose6d_pose_verify: best needs base_fit and base_flag");
-  const VerifyArgs a = {depth, F, H, W, depth_scale, K, K_per_frame, boxes_xyxy, frame_of, obj, verts, faces, voff,
+  const VerifyArgs a = {{depth, F, H, W, depth_scale, K, K_per_frame, boxes_xyxy, frame_of, obj}, verts, faces, voff,
                         nverts, toff, ntri, diam, n_slots, quat, trans, G, tau, counts, fit, agree, resid, verified,
                         zbuf_out, cls_out, base_fit, base_flag, best};
   pose_verify_kernel<<<(unsigned)N, kThreads, 0, p6::stream_of(stream)>>>(a);

@@ -401,7 +401,9 @@ int pose6d_crop_detections(const uint8_t *frames, int32_t bgr, const uint16_t *d
  * Translation: boxes_xyxy != NULL (the RGB and RGBD scripts, inference_rgb.py:99-104):
  * z = (double)trans[2], x = (c_x_box - cx) * z / fx, y alike; NULL: (double)trans.
  * Rotation: scipy's Rotation.from_quat(q).as_matrix() -- cast to double, divide by the
- * norm, the unit-quaternion matrix.  Projection: p = R c + t, z = max(p.z, 0.001),
+ * norm, the unit-quaternion matrix (csrc/pose_geom.h's quat_load / quat_unit / quat_to_mat,
+ * which the two depth stages below share; the sign quat_unit may flip cancels in every entry
+ * of the matrix).  Projection: p = R c + t, z = max(p.z, 0.001),
  * u = p.x * K00 / z + K02, v alike.
  * Outputs (each may be NULL): trans_out [N][3] double, pts_out [N][12][2] double,
  * pix_out [N][12][2] int64 = the points truncated toward zero (numpy's astype(int));
@@ -426,8 +428,9 @@ int pose6d_pose_project(const float *quat, const float *trans, const int32_t *bo
  * off / npts / diam / n_slots of pose6d_add_eval; quat [N][4] fp32 (x, y, z, w), model
  * -> camera, normalised in double here; trans [N][3] double.
  * Samples: G x G per box, sample k = j * G + i at pixel u = x1 + floor((2i + 1)(x2 -
- * x1) / (2G)), v alike from j, y1, y2 (integers).  Valid inside the frame with depth >
- * 0; back-projected in double, z = d * depth_scale, x = (u - cx) * z / fx, y alike,
+ * x1) / (2G)), v alike from j, y1, y2 (integers): csrc/pose_geom.h's sample_pixel, which
+ * pose6d_pose_verify calls too.  Valid inside the frame with depth > 0 (its depth_at: 0
+ * outside the frame); back-projected in double, z = d * depth_scale, x = (u - cx) * z / fx, y alike,
  * every product rounded on its own; kept when sqrt(|p - trans|^2) <= gate * diam -- the
  * gate centre is the INITIAL translation in every iteration.
  * `iters` times: q = R^T (p - t) in double, rounded to fp32; the nearest mesh point by
@@ -470,12 +473,14 @@ int pose6d_depth_refine(const uint16_t *depth, int32_t F, int32_t H, int32_t W, 
  * pose6d_depth_refine; obj [N] int64 are slots of the packed TRIANGLE table: verts float
  * [sum V][3] metres, faces int32 [sum T][3] (indices local to the object), voff / nverts /
  * toff / ntri int32 [n_slots] (first vertex, vertex count, first triangle, triangle
- * count), diam double [n_slots].  quat [N][4] fp32 (x, y, z, w), normalised in double as
- * pose6d_depth_refine does; trans [N][3] double.
+ * count), diam double [n_slots].  quat [N][4] fp32 (x, y, z, w), normalised in double by
+ * the code pose6d_depth_refine runs (csrc/pose_geom.h's read_detection: one header reader
+ * for both entry points); trans [N][3] double.
  * Vertices: c = R m + t, each row summed left to right; pu = c.x * fx / c.z + cx, pv
  * alike.  A triangle is skipped when an index is outside [0, nverts) (never
  * dereferenced), a vertex has c.z <= 0.001 or a projected coordinate is not finite.
- * Samples: pose6d_depth_refine's G x G grid, sample k = j * G + i at the integer pixel p.
+ * Samples: pose6d_depth_refine's G x G grid (the same sample_pixel), sample k = j * G + i
+ * at the integer pixel p.
  * Coverage: e(a, b, p) = (b.u - a.u)(p.v - a.v) - (b.v - a.v)(p.u - a.u); w0 = e(v1, v2,
  * p), w1 = e(v2, v0, p), w2 = e(v0, v1, p), s = (w0 + w1) + w2; covered when all three w
  * >= 0 and s > 0, or all three <= 0 and s < 0 (both windings, inclusive edges, no
